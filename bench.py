@@ -9,14 +9,21 @@ fixed forward command (0.5, 0, 0), no domain randomisation, actions U(-1,1) pre-
 HBM (synthetic).  Multi-GPU: one process per GPU (torch.distributed.run), envs sharded with no
 data-path collective (weak scaling); barrier + max-over-ranks timing over RCCL.
 
-  python bench.py [--gpus N --steps K --warmup W --envs E --dr --gather --no-cpu-baseline]
+  python bench.py [--gpus N --steps K --warmup W --envs E --dr --gather --dump-outputs DIR --full]
+
+A plain run sets up, pre-warms, runs the W warmup steps, times the K steps, writes the last step's
+outputs if --dump-outputs DIR is given (dump_outputs) and prints the JSON result line.  Everything
+else the benchmark can measure or check runs only with --full: the timed window replayed as
+single-step launches (timed, checked bit-equal) and from an idle GPU, the latency floor at E/2
+envs, the host-API rates, the contact-cap / one-step-error / line-search / drift measurements
+against the oracle, the CPU baseline, the gather timed alone and gather_check.
 
 Multi-GPU: `python bench.py --gpus N` starts N rank processes itself (launch_ranks: RANK /
 LOCAL_RANK / WORLD_SIZE set per child, before this process touches HIP) and relays rank 0's JSON
 line; under torch.distributed.run (WORLD_SIZE already set) the process is one rank and --gpus
 must equal WORLD_SIZE.  No torch: ranks talk through the library's own RCCL communicator
 (pp3_comm_*: barrier, max-over-ranks timing, the --gather collective), created from an id
-exchanged by a file rendezvous on the node.  With N > 1 every run also checks the multi-rank
+exchanged by a file rendezvous on the node.  With N > 1 a --full run also checks the multi-rank
 gather once, untimed (gather_check: per-rank checksums of the packed rows vs what landed at the
 root and in the all-gather).
 """
@@ -396,6 +403,41 @@ def qpos_drift(env, nsub=1000, dr_row=None, terrain_row=None):
     return float(np.abs(g - o).max() / np.abs(o).max())
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, env, last_actions_ptr=None, gather_dst=None):
+    """--dump-outputs: what the last timed step left in the env's buffers, as <out_dir>/<name>.npy,
+    so that two builds run with the same arguments can be compared output for output.  obs, reward,
+    done, metrics: float32 [E, n]; state: the state record as float64 (its two RNG words as their
+    integer values, not as the float bit patterns the device holds); actions: the policy's last
+    actions (--policy); gathered: what the hand-over delivered to this rank (--gather).  Over
+    DUMP_MAX_BYTES in all, every array keeps the same share of its rows, drawn with a fixed seed
+    (<name>.rows.npy holds their indices)."""
+    import numpy as np
+    from pupperv3_mjx import _abi, _lib
+    E = env.num_envs
+    arrays = {"obs": env._get(_abi.F_OBS), "reward": env._get(_abi.F_REWARD), "done": env._get(_abi.F_DONE),
+              "metrics": env._get(_abi.F_METRICS), "state": _oracle_record(env._get(_abi.F_STATE))}
+    if last_actions_ptr is not None:
+        a = np.empty((E, _abi.NU), np.float32)
+        _lib.check(env._L.pp3_memcpy_d2h(a.ctypes.data_as(C.c_void_p), C.c_void_p(last_actions_ptr), a.nbytes))
+        arrays["actions"] = a
+    if gather_dst is not None:
+        g = np.empty((gather_dst.nbytes // (4 * (env.observation_size + 2)), env.observation_size + 2), np.float32)
+        gather_dst.download(g)
+        arrays["gathered"] = g
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, int(a.shape[0] * (DUMP_MAX_BYTES // 2) / total))  # (half: room for the index files)
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], size=keep, replace=False))
+            np.save(os.path.join(out_dir, name + ".rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_ranks(n: int) -> int:
     """`bench.py --gpus N` without a launcher: start N rank processes (this script, RANK / LOCAL_RANK /
     WORLD_SIZE set, one GPU each), wait for them and return the job's exit status (rank 0 prints
@@ -504,8 +546,8 @@ def main():
     ap.add_argument("--launch", choices=("rollout", "step"), default="rollout",
                     help="rollout: the K timed steps as ONE fused launch (pp3_rollout, brax generate_unroll's "
                          "lax.scan with the actions given up front; per-step reward/done/obs trajectories written), "
-                         "then the same K steps as K single-step launches from the same start state, timed too and "
-                         "checked bit-equal; step: K single-step launches only (pp3_step)")
+                         "with --full then the same K steps as K single-step launches from the same start state, timed "
+                         "too and checked bit-equal; step: K single-step launches only (pp3_step)")
     ap.add_argument("--no-prewarm", action="store_true",
                     help="skip the ~200 ms untimed GPU pre-warm (state restored after it) before the warmup steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -514,7 +556,19 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the untimed accuracy / contact-cap measurements (profiling runs)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the single-step replay of the timed window "
+                         "and its bit-equality check, the idle-start replay, the latency floor, the host-API rates, "
+                         "the contact-cap / accuracy / line-search measurements against the oracle, the CPU baseline, "
+                         "the gather timed alone and the N > 1 gather_check (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step left (rank 0's shard: obs, reward, "
+                         "done, metrics, the state record; the policy's actions, the gathered rows) as DIR/<name>.npy")
     args = ap.parse_args()
+    full = args.full
+    if not full:
+        # a plain run sets up, warms up, times the K steps and prints the result line; nothing else
+        args.no_cpu_baseline = args.no_latency_floor = args.no_extras = args.no_gather_check = True
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         sys.exit(launch_ranks(args.gpus))  # this process only spawns the ranks (no HIP here)
@@ -524,8 +578,11 @@ def main():
     if args.gpus is not None and args.gpus != world:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     if args.dry_launch:
-        print(json.dumps({"rank": rank, "local_rank": local_rank, "world": world, "pid": os.getpid(),
-                          "launch": os.environ.get("PP3_LAUNCH_ID")}), flush=True)
+        # the line and its newline in ONE write: the ranks share this stdout, and with an unbuffered
+        # stdout (PYTHONUNBUFFERED) print() writes them apart, so two ranks' lines could run together
+        sys.stdout.write(json.dumps({"rank": rank, "local_rank": local_rank, "world": world, "pid": os.getpid(),
+                                     "launch": os.environ.get("PP3_LAUNCH_ID")}) + "\n")
+        sys.stdout.flush()
         return
     # rehearsal knob for the multi-rank code on one GPU (never used by the driver): every rank on
     # this device
@@ -678,7 +735,7 @@ def main():
             _lib.check(L.pp3_rollout_policy(env._h, policy._h, args.warmup, acts.ptr, None, None, None, None))
         else:
             _lib.check(L.pp3_step_timed(env._h, acts.ptr, E * 12, args.warmup, C.byref(ms)))
-    if rollout or policy is not None:
+    if (rollout or policy is not None) and full:
         snap = dev_snapshot()  # the timed window's start state
 
     env.synchronize()
@@ -710,8 +767,11 @@ def main():
     env.synchronize()
     barrier()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env, act_at(total - 1) if policy is not None else None, gather_dst)
     per_step, idle_start = None, None
-    if rollout:
+    end = None
+    if rollout and full:
         # the same K steps again as K single-step launches (HIP events) from the kept start state,
         # queued right behind the timed window (the rollout's end state kept on the device first)
         K, D = args.steps, env.observation_size
@@ -745,7 +805,7 @@ def main():
         # 0.2 s host pause, so the GPU starts it from the clock state of an idle device instead of
         # behind the pre-warm; HIP events, like the timed window's kernel_ms.  Not `value`.  (Not in
         # --no-extras profiling runs: their kernel stats keep to the timed launch.)
-    if rollout and not args.no_extras:
+    if rollout and full and not args.no_extras:
         dev_restore(snap)
         env.synchronize()
         time.sleep(0.2)
@@ -764,12 +824,15 @@ def main():
         if not idle_same:
             print(f"rank {rank}: idle-start replay differs from the timed rollout", file=sys.stderr, flush=True)
     if rollout:
-        for b in snap.values():
+        for b in (snap or {}).values():
             b.free()
-        if not unroll_gather:  # (the unroll hand-over is timed alone below, on these buffers)
+        if not (unroll_gather and full):  # (the unroll hand-over is timed alone below, on these buffers)
             for b in traj:
                 b.free()
-    if policy is not None:
+    if policy is not None and not full:
+        for b in traj:
+            b.free()
+    if policy is not None and full:
         # the same K steps again as the unfused loop (per step a pp3_policy_act launch on the obs
         # buffer, then a single-step launch) from the kept start state: actions and end state must
         # be bit-equal to the fused launch's
@@ -812,9 +875,12 @@ def main():
     # hashes across kernel builds mean the A/B variants ran the same trajectories, so a timing
     # difference is code speed, not a changed workload
     import hashlib
-    state_sha16 = hashlib.sha256((end[_abi.F_STATE] if (rollout or policy is not None) else env._get(_abi.F_STATE)).tobytes()).hexdigest()[:16]
+    state_sha16 = hashlib.sha256((end[_abi.F_STATE] if end is not None else env._get(_abi.F_STATE)).tobytes()).hexdigest()[:16]
     gather_info = None
-    if args.gather and not unroll_gather:
+    if not full:
+        if kernel_ms is None:  # (the per-step hand-over loop has no kernel-only time of its own)
+            kernel_ms = wall * 1e3
+    elif args.gather and not unroll_gather:
         # untimed: the same K steps' kernels alone (events), then the gather alone
         _lib.check(L.pp3_step_timed(env._h, C.c_void_p(act_at(args.warmup)), E * 12, args.steps, C.byref(ms)))
         kernel_ms = ms.value
@@ -925,7 +991,7 @@ def main():
                        "gather": gather_info, "gather_check": gcheck, "comm": comm_kind, "auto_reset_episode_length": args.auto_reset or None,
                        "policy_in_loop": args.policy or None},
             "launch": (f"rollout: the {K} timed steps fused into one pp3_rollout launch (per-step reward/done/obs "
-                       "trajectories written); per_step_launch = the same steps as single-step launches"
+                       "trajectories written); per_step_launch (--full) = the same steps as single-step launches"
                        if rollout else
                        ("policy: pp3_rollout_policy, the K steps as ONE fused launch (8-wave workgroups of 16 envs run "
                         "the MLP before each step; action/reward/done/obs trajectories written); per_step_launch = "

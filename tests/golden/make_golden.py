@@ -30,6 +30,29 @@ def main():
     with open(os.path.join(HERE, "obstacles_golden.json"), "w") as f:
         json.dump(out, f, indent=1)
     print("wrote", len(out), "cases")
+    print("wrote", meshes(), "meshes")
+
+
+MESH_TRIANGLES = 2000
+
+
+def meshes():
+    """meshes/stl/: the robot's 13 visual meshes (binary STL), each cut to its first MESH_TRIANGLES
+    triangles so that the fixtures stay small: what tests/test_render.py needs is real mesh files
+    under the names the model's <asset> section gives, not the whole surfaces."""
+    import struct
+    src, dst = os.path.join(REF, "meshes", "stl"), os.path.join(HERE, "meshes", "stl")
+    os.makedirs(dst, exist_ok=True)
+    names = sorted(f for f in os.listdir(src) if f.endswith(".stl"))
+    for name in names:
+        with open(os.path.join(src, name), "rb") as f:
+            header = f.read(80)
+            n = min(struct.unpack("<I", f.read(4))[0], MESH_TRIANGLES)
+            body = f.read(50 * n)
+        assert len(body) == 50 * n, name
+        with open(os.path.join(dst, name), "wb") as f:
+            f.write(header + struct.pack("<I", n) + body)
+    return len(names)
 
 
 if __name__ == "__main__":

@@ -84,7 +84,7 @@ def test_gather_across_rank_processes(loopback_env, tmp_path, world, G):
 
 def _bench(env, *extra, timeout=240):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--envs", "512",
-           "--no-cpu-baseline", "--no-latency-floor", "--no-extras", "--no-prewarm", *extra]
+           "--full", "--no-cpu-baseline", "--no-latency-floor", "--no-extras", "--no-prewarm", *extra]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -147,7 +147,8 @@ def test_bench_under_torch_distributed_run(loopback_env):
     env = {k: v for k, v in loopback_env.items() if k != "PP3_LAUNCH_ID"}  # keyed by the launcher
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--envs", "256", "--no-cpu-baseline", "--no-latency-floor", "--no-extras", "--no-prewarm"]
+           "--warmup", "1", "--envs", "256", "--full", "--no-cpu-baseline", "--no-latency-floor", "--no-extras",
+           "--no-prewarm"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]

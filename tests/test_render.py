@@ -11,7 +11,8 @@ import common
 from oracle import render_ref
 from pupperv3_mjx import MODEL_XML, mjcf, render
 
-REF_MESHES = "/root/reference/meshes/stl"  # present in the build container only (skipped elsewhere)
+# the robot's 13 visual meshes, each cut to its first 2000 triangles (golden/make_golden.py)
+REF_MESHES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "meshes", "stl")
 
 
 def _home_q():
@@ -38,7 +39,6 @@ def test_stl_binary_and_ascii(tmp_path):
     np.testing.assert_array_equal(render.load_stl(str(a)), tri)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MESHES), reason="reference mesh files not present")
 def test_reference_meshes_load_and_replace_proxies():
     t = render.load_stl(os.path.join(REF_MESHES, "BodyV4v70_001.stl"))
     with open(os.path.join(REF_MESHES, "BodyV4v70_001.stl"), "rb") as f:

@@ -15,7 +15,7 @@ for rep in $(seq 1 $REPS); do
       tag=$(basename $so .so)
       log=gpurun_out/ab/${tag}_s${i}_$rep.log
       envf=ab/$tag.env  # optional KEY=VALUE lines for this variant (e.g. PP3_NO_CULL=1)
-      env PP3_LIB_PATH=$PWD/$so $( [ -f $envf ] && cat $envf ) timeout -k 10 150 python3 bench.py $flags --no-cpu-baseline --no-extras --no-latency-floor > $log 2>&1
+      env PP3_LIB_PATH=$PWD/$so $( [ -f $envf ] && cat $envf ) timeout -k 10 150 python3 bench.py --full $flags --no-cpu-baseline --no-extras --no-latency-floor > $log 2>&1
       python3 -c "import json,sys; d=json.loads(open('$log').read().strip().split('\n')[-1]); print('$tag', 'set$i', $rep, d['value'], d['roofline']['avg_launch_ms'], d.get('per_step_launch') and d['per_step_launch']['avg_launch_ms'], d.get('state_sha16'))"
     done
   done

@@ -3,7 +3,7 @@
 #   -> gpurun_out/$TAG/pmc_flops ; summarise with tools/summarize_flops.py gpurun_out/$TAG
 set -e
 TAG=${1:-flops}
-ARGS=${2:---steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras}
+ARGS=${2:---full --steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null

@@ -4,7 +4,7 @@
 # (tools/summarize_profile.py) -> gpurun_out/$TAG/<variant>/.   tools/gpu_pmc_ab.sh TAG
 set -e
 TAG=${1:-pmc_ab}
-ARGS="--steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras"
+ARGS="--full --steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras"
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 for so in ab/*.so; do
   v=$(basename $so .so)

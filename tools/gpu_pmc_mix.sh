@@ -2,7 +2,7 @@
 # Instruction-mix PMC passes for env_step_kernel (each wave issues at most one instruction per
 # 4-cycle slot, of any type, so the per-type counts say where the wave's issue slots go).
 TAG=${1:-mix}
-ARGS=${2:---steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras}
+ARGS=${2:---full --steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null

@@ -3,7 +3,7 @@
 # and LDS loads share lgkmcnt, so a scalar miss also lengthens the LDS waits behind it).
 # One rocprofv3 --pmc run per pass, each under its own time limit; stops at the first failure.
 TAG=${1:-sqc}
-ARGS=${2:---steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras}
+ARGS=${2:---full --steps 50 --warmup 5 --no-cpu-baseline --no-latency-floor --no-extras}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null

@@ -13,7 +13,7 @@ if [ "${2:-tests}" = tests ]; then
   echo "tests_rc=$rc"; tail -n 25 $OUT/gpu_tests.log
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
-timeout -k 10 240 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { echo bench failed; tail -20 $OUT/bench_driver.err; exit 1; }
+timeout -k 10 240 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { echo bench failed; tail -20 $OUT/bench_driver.err; exit 1; }
 tail -c 3000 $OUT/bench_driver.json
 bash tools/gpu_profile.sh $TAG/prof || { echo profile failed; exit 1; }
 echo done
