@@ -71,10 +71,20 @@ template <int N>
 struct alignas(16) LaneTab {
   float g[N][32][4];
 };
-// the narrow phase's pair records, laid out the same way (lane = pair within a 32-pair batch)
+// the narrow phase's pair records, laid out the same way per 32-pair batch (lane = pair within the
+// batch): the six PairRec word groups of pair p and, as a seventh, the first word group of its
+// PairCon (what store_contact reads), 512 bytes apart, so one 32-bit offset reaches all seven
+// through the loads' immediate field
+constexpr int PAIR_GROUPS = PAIR_REC / 4 + 1;
 struct alignas(16) PairTab {
-  float g[PAIR_REC / 4][PP3_MAX_PAIR][4];
+  float g[PP3_MAX_PAIR / 32][PAIR_GROUPS][32][4];
 };
+static_assert(PP3_MAX_PAIR % 32 == 0, "PairTab: whole 32-pair batches");
+// byte offset of pair p's word group 0 in PairTab (group k: + 512 k); the one definition of the
+// layout, for the host packing and every kernel
+__host__ __device__ constexpr unsigned pair_tab_byte(unsigned p) {
+  return (p >> 5) * (unsigned)(PAIR_GROUPS * 512) + (p & 31u) * 16u;
+}
 // phase "limits/friction/actuation": lane l < 24 = joint-limit side (j = 1 + l/2, hi side when
 // l is odd), lane l < 12 = frictionloss row of dof 6+l and actuator l
 enum {

@@ -140,10 +140,31 @@ template <int N>
 __device__ __forceinline__ LaneRec<N> fetch_rec(const LaneRec<N>& src) {
   return fetch_groups<N, 4>(src.f);
 }
+// the floats `off` bytes into a model table, the offset a 32-bit unsigned value: with the model's
+// uniform base the load takes it in one VGPR beside the SGPR base pair (a signed index makes the
+// compiler build a 64-bit address per load: v_mad_u64_u32 / v_add_co + v_addc_co and their fillers)
+template <class T>
+__device__ __forceinline__ const float* at_bytes(const T& tab, unsigned off) {
+  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(&tab) + off);
+}
+// the word groups `off` bytes into a table far from the model's start: the table's address is made
+// an opaque scalar first, or the compiler folds the table's offset into the 64-bit vector address
+// (v_add_co + v_addc_co again); global address space, which the opaque value no longer implies
+typedef __attribute__((address_space(1))) const v4f GV4;
+template <class T>
+__device__ __forceinline__ const GV4* far_groups(const T& tab, unsigned off) {
+  uint64_t b = (uint64_t)(uintptr_t)&tab;
+  asm("" : "+s"(b));
+  return (const GV4*)(uintptr_t)(b + off);
+}
 // lane l's phase record from a word-group-major table
 template <int N>
 __device__ __forceinline__ LaneRec<N> fetch_rec(const LaneTab<N>& t, int l) {
-  return fetch_groups<N, 4 * 32>(t.g[0][l]);
+  return fetch_groups<N, 4 * 32>(at_bytes(t, 16u * (unsigned)l));
+}
+// the four word groups of pair p's PairCon
+__device__ __forceinline__ const GV4* pair_con_groups(const DevModel& m, int p) {
+  return far_groups(m.pair_con, (unsigned)sizeof(PairCon) * (unsigned)p);
 }
 __device__ __forceinline__ int as_i(float f) { return __float_as_int(f); }
 
@@ -513,9 +534,9 @@ struct PairLoad {
 };
 __device__ __forceinline__ PairLoad load_pair(const DevModel& m, int p) {
   PairLoad r;
+  const GV4* g = far_groups(m.pair_rec, pair_tab_byte((unsigned)p));
 #pragma unroll
-  for (int k = 0; k < 6; k++) r.v[k] = *reinterpret_cast<const v4f*>(m.pair_rec.g[k][p]);
-  r.v[6] = *reinterpret_cast<const v4f*>(&m.pair_con[p]);
+  for (int k = 0; k < PAIR_GROUPS; k++) r.v[k] = g[32 * k];
   return r;
 }
 // the per-env terrain table and its row length, read once per collision pass (above the
@@ -1020,8 +1041,9 @@ __device__ __forceinline__ float ldl_arrow_solve(float (&a)[NV], float b, int l,
   for (int st = 0; st < 3; st++) {
 #pragma unroll
     for (int g = 0; g < 4; g++) col[20 * g + slot] = a[3 * g + st];
-    // the four pivots' rhs (lane 3 g + st of leg g) in one masked store, not one branch per leg
-    if (l < 12 && l - 3 * (l / 3) == st) col[20 * (l / 3) + 19] = b;
+    // the four pivots' rhs (lane 3 g + st of leg g) in one store on every lane, the other lanes'
+    // into the dummy lanes' slot (col[18], never used): no EXEC region around one ds_write
+    col[(l < 12 && pst == st) ? 20 * pg + 19 : NV] = b;
     SYNC();
     {
       const float pv = col[20 * pg + slot];
@@ -1060,11 +1082,15 @@ __device__ __forceinline__ float ldl_arrow_solve(float (&a)[NV], float b, int l,
     }
     SYNC();
   }
-  // base Schur complement and its rhs: ONE exchange; every lane then factors and solves it
-  if (l >= 12 && l < NV) {
+  // base Schur complement and its rhs: ONE exchange; every lane then factors and solves it.  The
+  // base rows' lanes store them; the other lanes store into col[48 .. 54], dead since the last
+  // round and not read below (seven ds_write on every lane, no EXEC region)
+  {
+    const bool base_row = l >= 12 && l < NV;
+    const int so = base_row ? 6 * (l - 12) : 48, bo = base_row ? 36 + (l - 12) : 54;
 #pragma unroll
-    for (int c = 0; c < 6; c++) col[6 * (l - 12) + c] = a[12 + c];
-    col[36 + (l - 12)] = b;
+    for (int c = 0; c < 6; c++) col[so + c] = a[12 + c];
+    col[bo] = b;
   }
   SYNC();
   float S[6][6], y[6];
@@ -1510,12 +1536,12 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
   {
     v4f v[5];
 #pragma unroll
-    for (int k = 0; k < 2; k++) v[k] = *reinterpret_cast<const v4f*>(m.lane_com.g[k][l]);
+    for (int k = 0; k < 2; k++) v[k] = *reinterpret_cast<const v4f*>(at_bytes(m.lane_com, 16u * (unsigned)l) + k * 128);
 #pragma unroll
     for (int k = 0; k < 2; k++)
       for (int c = 0; c < 4; c++) rc_pf.f[4 * k + c] = v[k][c];
 #pragma unroll
-    for (int k = 0; k < 3; k++) v[2 + k] = *reinterpret_cast<const v4f*>(m.lane_m.g[k][l]);
+    for (int k = 0; k < 3; k++) v[2 + k] = *reinterpret_cast<const v4f*>(at_bytes(m.lane_m, 16u * (unsigned)l) + k * 128);
 #pragma unroll
     for (int k = 0; k < 3; k++)
       for (int c = 0; c < 4; c++) rm_pf.f[4 * k + c] = v[2 + k][c];
@@ -1540,7 +1566,7 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
   {
     const int c = l >> 2;
     const int p = c < s.ncon ? s.con_pair[c < NC ? c : 0] : 0;
-    const v4f* src = reinterpret_cast<const v4f*>(&m.pair_con[p]);
+    const GV4* src = pair_con_groups(m, p);
 #pragma unroll
     for (int k = 0; k < 4; k++) pcv[k] = src[k];
   }
@@ -1743,7 +1769,9 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
 #pragma unroll
     for (int j = 0; j < NV; j++) { a[j] = s.M[dn][pnat(j)]; mrow[j] = a[j]; }
     const float x = ldl_arrow_solve(a, s.qfrc_smooth[dn], l, &s.x.L[0][0]);
-    if (l < NV) s.qacc_smooth[dn] = x;
+    // (every lane: lanes >= NV hold row NV - 1 too and return its x, the base block's last
+    // unknown, which every lane solves from the same exchange -- the same value to the same slot)
+    s.qacc_smooth[dn] = x;
   }
   SYNC();
   PHASE(4); l = opaque_lane(l);
@@ -1799,7 +1827,10 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
     cws = hsum(cws, h);
     csm = hsum(csm, h);
     use_smooth = cws > csm;
-    if (l < NV) s.qacc[l] = use_smooth ? s.qacc_smooth[l] : s.qws[l];
+    {  // (lanes >= NV repeat lane NV - 1's copy: straight-line code instead of an EXEC region)
+      const int lc = l < NV ? l : NV - 1;
+      s.qacc[lc] = use_smooth ? s.qacc_smooth[lc] : s.qws[lc];
+    }
   }
   SYNC();
   PHASE(5); l = opaque_lane(l);
@@ -1927,7 +1958,7 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
         }
         PHASE(14); l = opaque_lane(l);
         const float x = ldl_arrow_solve(a, s.grad[dn], l, &s.x.L[0][0]);
-        if (l < NV) s.search[dn] = -x;
+        s.search[dn] = -x;  // (every lane, as for qacc_smooth)
       } else {
         dense_search<NC>((LdsShared<NC>*)&s, l, h, cmax, ncon, lsup);
       }
@@ -2110,13 +2141,22 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
     }
 #endif
     live = live && alpha != 0.0f;
-    if (live && l < NV) s.qacc[l] += alpha * s.search[l];
+    {  // qacc += alpha * search on the live half, as a select on every lane (lanes >= NV repeat
+      // lane NV - 1's update; a finished half stores its value back unchanged)
+      const int lc = l < NV ? l : NV - 1;
+      const float qa = s.qacc[lc];
+      const float qn = qa + alpha * s.search[lc];
+      s.qacc[lc] = live ? qn : qa;
+    }
     SYNC();
   }
-  if (l < NV) s.qws[l] = s.qacc[l];
   // the forward's velocity, kept for the sensors of the pipeline record (efc_aref is dead until
-  // the next substep rebuilds its rows)
-  if (l < NV) s.efc_aref[l] = s.qvel[l];
+  // the next substep rebuilds its rows); lanes >= NV repeat lane NV - 1's two copies
+  {
+    const int lc = l < NV ? l : NV - 1;
+    s.qws[lc] = s.qacc[lc];
+    s.efc_aref[lc] = s.qvel[lc];
+  }
   SYNC();
   return weight;  // the Euler step follows in the next substep's kinematics or in euler_step
 }
@@ -2906,7 +2946,7 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
     r_slip = (vx * vx + vy * vy) * (fcm ? 1.0f : 0.0f);
   }
   if (l < ncon_r && cdist < 0.0f) {  // geom_collision: (contact, id) matches with dist < 0
-    const v4f kb = reinterpret_cast<const v4f*>(&m.pair_con[cpair])[3];  // knee, body counts (host)
+    const v4f kb = pair_con_groups(m, cpair)[3];  // knee, body counts (host)
     r_knee = kb[1];
     r_body = kb[2];
   }
@@ -3596,8 +3636,9 @@ static int build_devmodel(const pp3_model_t* mm, const pp3_env_config_t* c, DevM
       if (r.kind == PK_SPHERE_BOX)
         for (int k = 0; k < 3; k++) r.half[k] = d->cg_size[g2][k];
       const float* rf = reinterpret_cast<const float*>(&r);
+      float* g = reinterpret_cast<float*>(reinterpret_cast<char*>(&d->pair_rec) + pair_tab_byte((unsigned)p));
       for (int k = 0; k < PAIR_REC / 4; k++)
-        for (int c = 0; c < 4; c++) d->pair_rec.g[k][p][c] = rf[4 * k + c];
+        for (int c = 0; c < 4; c++) g[128 * k + c] = rf[4 * k + c];
     }
     {  // contact-side record
       PairCon& q = d->pair_con[p];
@@ -3611,6 +3652,8 @@ static int build_devmodel(const pp3_model_t* mm, const pp3_env_config_t* c, DevM
       q.b = d->pair_b[p];
       q.k = d->pair_k[p];
       for (int k = 0; k < 5; k++) q.solimp[k] = d->pair_solimp[p][k];
+      // its first word group (sup, dm, mu) rides with the pair record: PairTab's seventh group
+      memcpy(reinterpret_cast<char*>(&d->pair_rec) + pair_tab_byte((unsigned)p) + 512 * (PAIR_GROUPS - 1), &q, 16);
     }
     if (mm->cgeom_margin[g1] != 0 || mm->cgeom_margin[g2] != 0) return set_err(PP3_ERR_MODEL, "nonzero geom margins unsupported");
   }
