@@ -510,6 +510,47 @@ int pp3_rollout_policy_timed(pp3_env_t* env, pp3_policy_t* policy, int32_t nstep
                              float* reward_dev, float* done_dev, float* obs_dev, float* kernel_ms_total);
 const char* pp3_policy_last_error(void);
 
+/* ---- Stochastic policy: Brax PPO's data-collection actor (additive; PP3_ABI_VERSION stays 2) ----
+ * The training form of the network keeps the whole Gaussian head: a linear last layer of 24
+ * columns, loc = y[0:12] and s = y[12:24] (pupperv3_mjx/export.py convert_training_params).
+ * NormalTanhDistribution ([ext] brax 0.12.1 training/distribution.py; quoted from memory):
+ *   scale = (softplus(s) + min_std) * var_scale        (Brax: min_std 0.001, var_scale 1)
+ *   raw = loc + scale * eps, action = tanh(raw),
+ *   log_prob = sum_j [ normal_logpdf(raw_j; loc_j, scale_j) - 2 (log 2 - raw_j - softplus(-2 raw_j)) ]
+ * eps is jax.random.normal(key, (N, 12)) restated on the library's threefry: sqrt(2) * erfinv of
+ * jax.random.uniform(key, (N, 12), nextafter(-1, 0), 1), the word of env i, column j being element
+ * i * 12 + j of the key's N * 12 random bits.  The uniform is bit-exact with jax; erfinv is the
+ * device library's, not bit-pinned to XLA's erf_inv, so eps agrees with jax to f32 rounding only. */
+enum { PP3_DIST_NONE = 0, PP3_DIST_NORMAL_TANH = 1 };
+/* Gives the policy its head.  PP3_ERR_ARG unless kind is PP3_DIST_NORMAL_TANH, the policy has 24
+ * outputs and a linear last layer, min_std >= 0 and var_scale > 0.  (A handle created with
+ * device < 0 holds the layer records only, no device memory: it serves this check and the queries
+ * on a host without a GPU, and every launch refuses it.) */
+int pp3_policy_set_distribution(pp3_policy_t* policy, int32_t kind, float min_std, float var_scale);
+/* One sample per row i < n from key (two host words): actions[i][0:12] = tanh(raw) (required),
+ * and where the pointer is not null raw[i][0:12] (row stride 12), logp[i] and logits[i][0:24] (the
+ * last layer as computed, row stride 24).  partitionable: the env config's rng_partitionable. */
+int pp3_policy_sample(pp3_policy_t* policy, const float* obs_dev, int64_t obs_stride, int32_t n,
+                      const uint32_t* key, int32_t partitionable, float* actions_dev, int64_t action_stride,
+                      float* raw_dev, float* logp_dev, float* logits_dev, void* stream);
+/* pp3_rollout_policy with the sampling actor in the loop: the data collection of brax's
+ * generate_unroll ([ext] brax 0.12.1 training/acting.py, from memory).  Key schedule: K_0 = key;
+ * at step t, (cur, next) = jax.random.split(K_t), the step samples with cur, K_{t+1} = next;
+ * key_out = K_nsteps (computed on the host), so unrolls chain.  The env's rng_partitionable
+ * selects the split and bits layout.  actions_dev f32[nsteps][N][12] (required: the env steps on
+ * it), raw_dev f32[nsteps][N][12] and logp_dev f32[nsteps][N] (optional), reward / done / obs as
+ * pp3_rollout_policy.  ONE launch for the nsteps steps where pp3_rollout_policy is one launch (the
+ * head runs in the workgroup's MLP, the chain advances on the device); otherwise per step a
+ * pp3_policy_sample launch with that step's key, then a step launch.  Bit for bit the same either
+ * way.  The policy needs a distribution, 36H inputs and the env's device. */
+int pp3_rollout_policy_sample(pp3_env_t* env, pp3_policy_t* policy, int32_t nsteps, const uint32_t* key,
+                              uint32_t* key_out, float* actions_dev, float* raw_dev, float* logp_dev,
+                              float* reward_dev, float* done_dev, float* obs_dev, void* stream);
+/* The same bracketed by HIP events on the handle's stream (kernel_ms_total = their elapsed time). */
+int pp3_rollout_policy_sample_timed(pp3_env_t* env, pp3_policy_t* policy, int32_t nsteps, const uint32_t* key,
+                                    uint32_t* key_out, float* actions_dev, float* raw_dev, float* logp_dev,
+                                    float* reward_dev, float* done_dev, float* obs_dev, float* kernel_ms_total);
+
 /* ---------------------------------------------------------------------------------------
  * Multi-GPU (no reference code: the reference runs one process per device under
  * Brax PPO's pmap, [ext] brax 0.12.1 brax/training/agents/ppo/train.py, where the env batch is

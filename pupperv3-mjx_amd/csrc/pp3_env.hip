@@ -2578,6 +2578,57 @@ __device__ __noinline__ void policy_mlp_tile(pp3pol::KNet* net, float* act, int 
   pp3pol::mlp_tile<pp3pol::KNet, pp3pol::LdsTileBuf, LdsObsTile, MLP_CG>(
       *net, nullptr, 0, act, NU, n, row0, *buf, threadIdx.x, in);
 }
+
+// The sampled policy rollout (pp3_rollout_policy_sample): the same kernel, the MLP's last layer
+// feeding the tanh-Gaussian head (pp3_mlp.h sample_head).  Its own argument record: PolicyStepArgs
+// keeps its layout.
+struct SamplePolicyStepArgs {
+  PolicyStepArgs p;
+  float* raw;       // [nsteps][N][12] pre-tanh samples, or null
+  float* logp;      // [nsteps][N], or null
+  uint32_t k0, k1;  // K_0 of the unroll's key chain
+  float min_std, var_scale;
+};
+typedef __attribute__((address_space(4))) const SamplePolicyStepArgs GSArgs;
+typedef __attribute__((address_space(3))) uint32_t LdsU32;
+// Sibling of policy_mlp / policy_mlp_tile for the sampled rollout, out of line for the same reason
+// (`in` null: the observations come from global memory).  The key chain of generate_unroll lives in
+// LDS, nothing of it in registers across the step: keys[0..1] / keys[2..3] hold K_it in slot it & 1;
+// thread 0 splits it into this step's sampling key (keys[4..5]) and K_{it+1} (the other slot: its
+// readers of two steps ago are many barriers back).  Everything else is re-read from the kernel
+// arguments (scalar loads through the uniform pointer).
+__device__ __noinline__ void policy_mlp_sample(GSArgs* ga, LdsObsTile* in, int it, int Hm, int part,
+                                               pp3pol::LdsTileBuf* buf, LdsU32* keys) {
+  using pp3pol::uni;
+  ga = uni(ga);
+  it = uni(it);
+  Hm = uni(Hm);
+  part = uni(part);
+  if (threadIdx.x == 0) {
+    const int sl = 2 * (it & 1);
+    const pp3pol::HeadKey kt{keys[sl], keys[sl + 1]};
+    const pp3pol::HeadKey cur = pp3pol::head_split2(kt, 0, part), nxt = pp3pol::head_split2(kt, 1, part);
+    keys[2 - sl] = nxt.a;
+    keys[3 - sl] = nxt.b;
+    keys[4] = cur.a;
+    keys[5] = cur.b;
+  }
+  __syncthreads();
+  const int N = ga->p.s.N;
+  pp3pol::SampleHead hd;
+  hd.raw = ga->raw ? ga->raw + (size_t)it * N * NU : nullptr;
+  hd.logp = ga->logp ? ga->logp + (size_t)it * N : nullptr;
+  hd.logits = nullptr;
+  hd.k0 = (uint32_t)uni((int)keys[4]);
+  hd.k1 = (uint32_t)uni((int)keys[5]);
+  hd.count = N * NU;
+  hd.part = part;
+  hd.min_std = ga->min_std;
+  hd.var_scale = ga->var_scale;
+  pp3pol::mlp_tile<pp3pol::KNet, pp3pol::LdsTileBuf, LdsObsTile, MLP_CG, pp3pol::SampleHead>(
+      ga->p.net, ga->p.s.obs_out, PP3_OBS_DIM * Hm, ga->p.act + (size_t)it * ga->p.s.act_stride, NU, N,
+      blockIdx.x * pp3pol::TILE, *buf, threadIdx.x, in, hd);
+}
 // Between the fused steps every global value a wave reads back was stored by a wave of the same
 // workgroup (the env step: by the same lane), so on the same CU: the acquire is at workgroup scope,
 // which the gfx942/950 memory model (non-tgsplit) serves from the CU's own L1 without an invalidate
@@ -2605,18 +2656,30 @@ __device__ __noinline__ void policy_mlp_tile(pp3pol::KNet* net, float* act, int 
 #endif
 // CULL: models with obstacle boxes (DevModel::cull_on) launch the instantiation with the
 // sphere-box cull of collision() compiled in; the flat model's code is the same without it
-template <int NC, bool FUSED, int NWV = 1, bool CULL = false>
+// SAMPLE: the policy rollout with the stochastic head (its own instantiation and argument record:
+// the others compile to what they were without it)
+template <int NC, bool FUSED, int NWV = 1, bool CULL = false, bool SAMPLE = false>
 __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
-    typename std::conditional<(NWV > 1), PolicyStepArgs, StepArgs>::type a_arg) {
+    typename std::conditional<SAMPLE, SamplePolicyStepArgs,
+                              typename std::conditional<(NWV > 1), PolicyStepArgs, StepArgs>::type>::type a_arg) {
   static_assert(NWV == 1 || (FUSED && NWV == pp3pol::NWAVE), "the policy rollout is fused, one MLP tile per workgroup");
+  static_assert(!SAMPLE || NWV > 1, "the stochastic head lives in the policy rollout");
   constexpr bool alias = PP3_AB_ALIAS && NWV == 1;
   __shared__ Shared<NC> sh[alias ? 1 : 2 * NWV];
   static_assert(NWV == 1 || sizeof(sh) >= pp3pol::TILE_BUF_BYTES, "the MLP's LDS scratch aliases the envs' blocks");
   // the policy rollout's observation tile (its own LDS, next to the env blocks): each env step
   // writes its env's new observation row into it, the next step's MLP reads it in place
-  __shared__ float obs_tile[NWV > 1 ? pp3pol::TILE : 1][OBS_TILE_W];
+  // (SAMPLE: one more row, the key chain's six words: policy_mlp_sample)
+  __shared__ float obs_tile[NWV > 1 ? pp3pol::TILE + (SAMPLE ? 1 : 0) : 1][OBS_TILE_W];
   int nsteps;
-  if constexpr (NWV > 1) nsteps = a_arg.s.nsteps;
+  if constexpr (SAMPLE) {
+    nsteps = a_arg.p.s.nsteps;
+    if (threadIdx.x == 0) {  // K_0 into slot 0 (the first step's barrier publishes it)
+      LdsU32* keys = (LdsU32*)&obs_tile[pp3pol::TILE][0];
+      keys[0] = a_arg.k0;
+      keys[1] = a_arg.k1;
+    }
+  } else if constexpr (NWV > 1) nsteps = a_arg.s.nsteps;
   else nsteps = FUSED ? a_arg.nsteps : 1;
   constexpr bool TG = true;  // trajectory rows (optional pointers) written by both kernels: free in the single-step one
 #ifdef PP3_PHASE_PROF
@@ -2667,7 +2730,13 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
     }
     __syncthreads();
     PP3_STEP_ACQUIRE();
-    {
+    if constexpr (SAMPLE) {
+      policy_mlp_sample((GSArgs*)ap, tile_in ? (LdsObsTile*)obs_tile : (LdsObsTile*)nullptr, it, Hm,
+                        ((const DevModel*)(const GModel*)a.m)->partitionable,
+                        (pp3pol::LdsTileBuf*)(reinterpret_cast<pp3pol::TileBuf*>(sh)),
+                        (LdsU32*)&obs_tile[pp3pol::TILE][0]);
+      PP3_STEP_ACQUIRE();
+    } else {
       if (tile_in)
         policy_mlp_tile(&pa.net, pa.act + (size_t)it * a.act_stride, a.N, blockIdx.x * pp3pol::TILE,
                         (pp3pol::LdsTileBuf*)(reinterpret_cast<pp3pol::TileBuf*>(sh)), (LdsObsTile*)obs_tile);
@@ -3285,6 +3354,7 @@ struct pp3_env {
   float* terrain;  // TerrainRec rows (pp3_set_terrain), null until first set
   int nbox;        // world box-geom slots in the model
   int cull;        // DevModel::cull_on: steps launch env_step_kernel<..., CULL = true>
+  int partitionable;  // the config's rng_partitionable (the sampled policy rollout's host key chain)
   hipEvent_t ev0, ev1;
 };
 
@@ -3851,6 +3921,7 @@ int pp3_create(const pp3_model_t* model, const pp3_env_config_t* cfg, int32_t nu
   e->N = num_envs;
   e->stride = hm.stride;
   e->H = hm.H;
+  e->partitionable = hm.partitionable;
   e->nbox = hm.nbox;
   e->cull = hm.cull_on;
   {
@@ -4096,6 +4167,134 @@ int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float
                                 false, (void*)st);
     if (rc) return rc;
   }
+  return PP3_OK;
+}
+
+}  // extern "C"
+
+// Host restatement of threefry and split(key)[i] (pp3_mlp.h head_threefry / head_split2 are the
+// device's), for the sampled rollout's key chain:
+// the per-step keys of the unfused path and the returned K_nsteps.
+static void host_threefry(uint32_t k0, uint32_t k1, uint32_t x0, uint32_t x1, uint32_t& y0, uint32_t& y1) {
+  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
+  static const int rot[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
+  x0 += k0;
+  x1 += k1;
+  for (int i = 0; i < 5; i++) {
+    for (int q = 0; q < 4; q++) {
+      x0 += x1;
+      x1 = (x1 << rot[i & 1][q]) | (x1 >> (32 - rot[i & 1][q]));
+      x1 ^= x0;
+    }
+    x0 += ks[(i + 1) % 3];
+    x1 += ks[(i + 2) % 3] + (uint32_t)(i + 1);
+  }
+  y0 = x0;
+  y1 = x1;
+}
+// jax.random.split(k)[i], i in {0, 1}
+static Key host_split2(Key k, int i, int part) {
+  Key r;
+  uint32_t y0, y1;
+  if (part) {
+    host_threefry(k.a, k.b, 0u, (uint32_t)i, y0, y1);
+    r.a = y0;
+    r.b = y1;
+  } else {  // flat words [y0(0,2), y0(1,3), y1(0,2), y1(1,3)]: key i = words 2i, 2i + 1
+    uint32_t a0, a1, b0, b1;
+    host_threefry(k.a, k.b, 0u, 2u, a0, a1);
+    host_threefry(k.a, k.b, 1u, 3u, b0, b1);
+    r.a = i ? a1 : a0;
+    r.b = i ? b1 : b0;
+  }
+  return r;
+}
+
+extern "C" {
+
+int pp3_rollout_policy_sample(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, const uint32_t* key, uint32_t* key_out,
+                              float* actions_dev, float* raw_dev, float* logp_dev, float* reward_dev, float* done_dev,
+                              float* obs_dev, void* stream) {
+  if (!e || !policy || !key || !key_out || !actions_dev)
+    return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: null argument");
+  if (nsteps < 1) return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: nsteps must be >= 1");
+  float min_std, var_scale;
+  if (!pp3_policy_distribution(policy, &min_std, &var_scale))
+    return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: the policy has no distribution (pp3_policy_set_distribution)");
+  if (pp3_policy_device(policy) != e->device)
+    return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: policy and env on different devices");
+  if (pp3_policy_net(policy)->in_dim != PP3_OBS_DIM * e->H)
+    return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: the policy's input width must equal the observation size 36 * observation_history");
+  const size_t on = (size_t)e->N * PP3_OBS_DIM * e->H;
+  const hipStream_t st = stream_of(e, stream);
+  const int part = e->partitionable;
+  const Key k0{key[0], key[1]};
+#ifndef PP3_PHASE_PROF
+  if (policy_rollout_fused(e)) {
+    // ONE launch, as pp3_rollout_policy: the workgroup's MLP ends in the head, the key chain
+    // advances in the kernel (env_step_kernel<8, true, 8, CULL, true>)
+    HIPCHK(hipSetDevice(e->device));
+    SamplePolicyStepArgs sa;
+    StepArgs& a = sa.p.s;
+    a.m = e->dmodel;
+    a.state = e->state;
+    a.obs_in = e->obs;
+    a.obs_out = e->obs;
+    a.actions = actions_dev;
+    a.reward = e->reward;
+    a.done = e->done;
+    a.metrics = e->metrics;
+    a.dr = e->dr_on ? e->dr : nullptr;
+    a.pipe = e->pipe_on ? e->pipe : nullptr;
+    a.episode = e->episode_length > 0 ? e->episode : nullptr;
+    a.first_state = e->first_state;
+    a.first_obs = e->first_obs;
+    a.episode_length = e->episode_length;
+    a.N = e->N;
+    a.repeat = 1;
+    a.phase = 0;
+    a.nsteps = nsteps;
+    a.act_stride = (int64_t)e->N * NU;
+    a.traj_reward = reward_dev;
+    a.traj_done = done_dev;
+    a.traj_obs = obs_dev;
+    sa.p.act = actions_dev;
+    sa.p.net = *pp3_policy_net(policy);
+    sa.raw = raw_dev;
+    sa.logp = logp_dev;
+    sa.k0 = k0.a;
+    sa.k1 = k0.b;
+    sa.min_std = min_std;
+    sa.var_scale = var_scale;
+    const dim3 grid((e->N + pp3pol::TILE - 1) / pp3pol::TILE), block(WAVE * pp3pol::NWAVE);
+    if (e->cull) hipLaunchKernelGGL((env_step_kernel<8, true, pp3pol::NWAVE, true, true>), grid, block, 0, st, sa);
+    else hipLaunchKernelGGL((env_step_kernel<8, true, pp3pol::NWAVE, false, true>), grid, block, 0, st, sa);
+    HIPCHK(hipGetLastError());
+    Key kt = k0;  // K_nsteps: the chain's `next` halves (host threefry)
+    for (int t = 0; t < nsteps; t++) kt = host_split2(kt, 1, part);
+    key_out[0] = kt.a;
+    key_out[1] = kt.b;
+    return PP3_OK;
+  }
+#endif
+  // per step: the sample launch with that step's key on the env's obs buffer, then the step launch
+  Key kt = k0;
+  for (int t = 0; t < nsteps; t++) {
+    const Key cur = host_split2(kt, 0, part);
+    kt = host_split2(kt, 1, part);
+    const uint32_t kw[2] = {cur.a, cur.b};
+    float* act = actions_dev + (size_t)t * e->N * NU;
+    if (pp3_policy_sample(policy, e->obs, PP3_OBS_DIM * e->H, e->N, kw, part, act, NU,
+                          raw_dev ? raw_dev + (size_t)t * e->N * NU : nullptr,
+                          logp_dev ? logp_dev + (size_t)t * e->N : nullptr, nullptr, (void*)st) != PP3_OK)
+      return set_err(PP3_ERR_ARG, std::string("pp3_rollout_policy_sample: ") + pp3_policy_last_error());
+    const int rc = launch_steps(e, act, 0, 1, reward_dev ? reward_dev + (size_t)t * e->N : nullptr,
+                                done_dev ? done_dev + (size_t)t * e->N : nullptr, obs_dev ? obs_dev + (size_t)t * on : nullptr,
+                                false, (void*)st);
+    if (rc) return rc;
+  }
+  key_out[0] = kt.a;
+  key_out[1] = kt.b;
   return PP3_OK;
 }
 
@@ -4457,6 +4656,21 @@ int pp3_rollout_policy_timed(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps,
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipEventRecord(e->ev0, e->stream));
   const int rc = pp3_rollout_policy(e, policy, nsteps, actions_dev, reward_dev, done_dev, obs_dev, e->stream);
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(e->ev1, e->stream));
+  HIPCHK(hipEventSynchronize(e->ev1));
+  HIPCHK(hipEventElapsedTime(kernel_ms_total, e->ev0, e->ev1));
+  return PP3_OK;
+}
+
+int pp3_rollout_policy_sample_timed(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, const uint32_t* key,
+                                    uint32_t* key_out, float* actions_dev, float* raw_dev, float* logp_dev,
+                                    float* reward_dev, float* done_dev, float* obs_dev, float* kernel_ms_total) {
+  if (!e || !policy || !key || !key_out || !actions_dev || !kernel_ms_total) return set_err(PP3_ERR_ARG, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipEventRecord(e->ev0, e->stream));
+  const int rc = pp3_rollout_policy_sample(e, policy, nsteps, key, key_out, actions_dev, raw_dev, logp_dev, reward_dev,
+                                           done_dev, obs_dev, e->stream);
   if (rc) return rc;
   HIPCHK(hipEventRecord(e->ev1, e->stream));
   HIPCHK(hipEventSynchronize(e->ev1));

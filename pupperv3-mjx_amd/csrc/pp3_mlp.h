@@ -2,6 +2,8 @@
 // stand-alone policy kernel (pp3_policy.hip mlp_kernel: pp3_policy_act) and the fused
 // policy-in-the-loop rollout (pp3_env.hip env_step_kernel<NC, true, 8>: pp3_rollout_policy).
 // One source for both, so the two compute the same instructions and give bit-identical actions.
+// With a SampleHead (pp3_policy_sample, pp3_rollout_policy_sample) the last layer feeds the
+// tanh-Gaussian sampling head below instead of being the action.
 //
 // Format: export.py:13-81 convert_params (dense layers, observation normalisation folded into
 // the first layer, final layer = the mean half of the Gaussian head, final activation tanh).
@@ -18,6 +20,8 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+
+#include <type_traits>
 
 #include "pupper_hip.h"
 
@@ -98,6 +102,132 @@ __device__ __forceinline__ Layer layer_of(NetT& net, int li) {
   return L;
 }
 
+// ---- The stochastic head: Brax PPO's tanh-Gaussian actor on the full 2 x 12 final layer ----
+// (export.py convert_training_params keeps both halves, linear).  Per env row, loc_j = y[j] and
+// s_j = y[12 + j]:
+//   scale_j  = (softplus(s_j) + min_std) * var_scale          ([ext] brax 0.12.1
+//              training/distribution.py NormalTanhDistribution, defaults min_std 0.001, var_scale 1:
+//              quoted from memory, Brax is not vendored in the reference)
+//   z_j      = sqrt(2) * erfinv(u_j), u_j = jax.random.uniform(key, (N, 12), minval =
+//              nextafter(-1, 0), maxval = 1)[env][j]: jax.random.normal's recipe on the threefry
+//              stream (the uniform is bit-exact with rng.uniform; the device library's erfinvf is
+//              not bit-pinned to XLA's erf_inv, so z agrees with jax to f32 rounding, not bitwise)
+//   raw_j    = loc_j + scale_j * z_j,   action_j = tanh(raw_j)
+//   log_prob = sum_j [ -zr_j^2 / 2 - log(scale_j) - log(2 pi) / 2 - 2 (log 2 - raw_j - softplus(-2 raw_j)) ]
+//              with zr_j = (raw_j - loc_j) / scale_j from the f32 raw_j as stored (what the learner's
+//              log_prob(logits, raw_action) recomputes), summed over j ascending.
+// No FMA contraction, so the stand-alone kernel and the fused rollout round alike.
+constexpr int HEAD_NU = PP3_NU;         // actions per env
+constexpr int HEAD_COLS = 2 * HEAD_NU;  // the head's final-layer width (two 16-column tiles)
+struct NoHead {};                       // mlp_tile's default: the deterministic (deployment) policy
+struct SampleHead {
+  float* raw;     // [n][12] pre-tanh samples, or null
+  float* logp;    // [n], or null
+  float* logits;  // [n][24] the final layer as computed (debug / tests), or null
+  uint32_t k0, k1;  // this step's key
+  int count, part;  // elements of the key's draw (N * 12), jax_threefry_partitionable
+  float min_std, var_scale;
+};
+
+// jax's threefry2x32 and the head's three uses of it (split(key)[i], the 32-bit random_bits word i
+// of `count`, uniform in [lo, 1)), restated here instead of calling pp3_device.h threefry / split_i /
+// bits_i / uniform_i: those are shared with the env kernels, and call sites with these argument
+// ranges (count = N * 12, word index up to N * 12, split into 2) joining them changed the code the
+// compiler emits for the env step and reset kernels (value ranges it propagates into the shared
+// helpers' arguments), which must stay what it was.  tests/test_gpu_policy_sample.py pins these
+// to the host rng bit for bit, as tests/test_gpu_env.py pins the others.
+struct HeadKey { uint32_t a, b; };
+__device__ __forceinline__ void head_threefry(uint32_t k0, uint32_t k1, uint32_t x0, uint32_t x1, uint32_t& y0,
+                                              uint32_t& y1) {
+  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
+  x0 += k0;
+  x1 += k1;
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    const int r0 = (i & 1) ? 17 : 13, r1 = (i & 1) ? 29 : 15, r2 = (i & 1) ? 16 : 26, r3 = (i & 1) ? 24 : 6;
+    x0 += x1; x1 = (x1 << r0) | (x1 >> (32 - r0)); x1 ^= x0;
+    x0 += x1; x1 = (x1 << r1) | (x1 >> (32 - r1)); x1 ^= x0;
+    x0 += x1; x1 = (x1 << r2) | (x1 >> (32 - r2)); x1 ^= x0;
+    x0 += x1; x1 = (x1 << r3) | (x1 >> (32 - r3)); x1 ^= x0;
+    x0 += ks[(i + 1) % 3];
+    x1 += ks[(i + 2) % 3] + (uint32_t)(i + 1);
+  }
+  y0 = x0;
+  y1 = x1;
+}
+// jax.random.split(k)[i], i in {0, 1}
+__device__ __forceinline__ HeadKey head_split2(HeadKey k, int i, int part) {
+  HeadKey r;
+  uint32_t y0, y1;
+  if (part) {
+    head_threefry(k.a, k.b, 0u, (uint32_t)i, y0, y1);
+    r.a = y0;
+    r.b = y1;
+  } else {  // flat words [y0(0,2), y0(1,3), y1(0,2), y1(1,3)]: key i = words 2i, 2i + 1
+    head_threefry(k.a, k.b, 0u, 2u, y0, y1);
+    r.a = i ? y1 : y0;
+    head_threefry(k.a, k.b, 1u, 3u, y0, y1);
+    r.b = i ? y1 : y0;
+  }
+  return r;
+}
+// jax.random.uniform(key, (count,), minval = lo, maxval = 1)[i], float32, bit-exact with jax
+__device__ __forceinline__ float head_uniform(HeadKey k, int count, int i, float lo, int part) {
+#pragma clang fp contract(off)
+  uint32_t y0, y1, w;
+  if (part) {
+    head_threefry(k.a, k.b, 0u, (uint32_t)i, y0, y1);
+    w = y0 ^ y1;
+  } else {  // the counters 0 .. count-1 (padded to even with a 0) split in halves: x0 = first, x1 = second
+    const int h = (count + (count & 1)) / 2;
+    const int lane = i % h, half = i / h;
+    head_threefry(k.a, k.b, (uint32_t)lane, (lane + h >= count) ? 0u : (uint32_t)(lane + h), y0, y1);
+    w = half ? y1 : y0;
+  }
+  const float f = __uint_as_float((w >> 9) | 0x3F800000u) - 1.0f;
+  const float v = f * (1.0f - lo) + lo;
+  return v > lo ? v : lo;
+}
+
+__device__ __forceinline__ float softplus(float x) {
+#pragma clang fp contract(off)
+  return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));
+}
+
+// Y: the final layer's 16 x 32 outputs in LDS (a barrier since they were written).  Threads
+// 0 .. 191 sample one (row, j) each and leave the log-prob term in columns 32 .. 43 of the row;
+// after a barrier threads 0 .. 15 sum their row.  Ends with a barrier (Y is free again).
+template <class RowsT>
+__device__ __forceinline__ void sample_head(RowsT& Y, const SampleHead& hd, float* __restrict__ act, int act_stride,
+                                            int n, int row0, int tid) {
+#pragma clang fp contract(off)
+  const int r = tid / HEAD_NU, j = tid - r * HEAD_NU;
+  const int row = row0 + r;
+  if (tid < TILE * HEAD_NU && row < n) {
+    const float loc = Y[r][j], s = Y[r][HEAD_NU + j];
+    const float scale = (softplus(s) + hd.min_std) * hd.var_scale;
+    const float u = head_uniform(HeadKey{hd.k0, hd.k1}, hd.count, row * HEAD_NU + j, -0x1.fffffep-1f, hd.part);
+    const float z = 1.41421356f * erfinvf(u);
+    const float raw = loc + scale * z;
+    const float zr = (raw - loc) / scale;
+    Y[r][2 * TILE + j] =
+        -0.5f * zr * zr - logf(scale) - 0.918938533f - 2.0f * (0.693147181f - raw - softplus(-2.0f * raw));
+    act[(size_t)row * act_stride + j] = tanhf(raw);
+    if (hd.raw) hd.raw[(size_t)row * HEAD_NU + j] = raw;
+    if (hd.logits) {
+      hd.logits[(size_t)row * HEAD_COLS + j] = loc;
+      hd.logits[(size_t)row * HEAD_COLS + HEAD_NU + j] = s;
+    }
+  }
+  __syncthreads();
+  if (tid < TILE && row0 + tid < n && hd.logp) {
+    float sum = 0.0f;
+    for (int q = 0; q < HEAD_NU; q++) sum += Y[tid][2 * TILE + q];
+    hd.logp[row0 + tid] = sum;
+  }
+  __syncthreads();
+}
+
 // The MLP of observation rows row0 .. row0+15 (rows >= n read as zero, get no action) ->
 // act[row * act_stride + col] for col < out_dim.  Called by all 64 * NWAVE threads of the
 // workgroup (tid = threadIdx.x); `buf` is the workgroup's LDS scratch.  Ends with a barrier.
@@ -109,10 +239,14 @@ __device__ __forceinline__ Layer layer_of(NetT& net, int li) {
 // CG: groups of 4 k-blocks per chunk (8 in the stand-alone kernel; the fused rollout's out-of-line
 // call uses 4, whose registers fit the callee's caller-saved VGPRs: no save / restore through
 // scratch per call).  The MFMA sequence does not depend on it.
-template <class NetT, class BufT = TileBuf, class InT = TileRows, int CG = CG8>
+// HeadT: NoHead (the last layer's activations are the actions) or SampleHead: the last layer (24
+// linear columns) stays in LDS and sample_head draws the actions from it (act = the tanh'ed
+// samples); a compile-time choice, the NoHead code is what it was without it.
+template <class NetT, class BufT = TileBuf, class InT = TileRows, int CG = CG8, class HeadT = NoHead>
 __device__ __forceinline__ void mlp_tile(NetT& net, const float* __restrict__ obs, int obs_stride,
                                          float* __restrict__ act, int act_stride, int n, int row0, BufT& buf,
-                                         int tid, InT* in = nullptr) {
+                                         int tid, InT* in = nullptr, HeadT head = HeadT()) {
+  constexpr bool SAMPLE = std::is_same<HeadT, SampleHead>::value;
   // the wave index is wave-uniform: readfirstlane says so, so the tile / chunk / group loops below
   // become scalar branches instead of exec-mask divergence
   const int lane = tid & 63, wave = uni(tid >> 6);
@@ -183,7 +317,7 @@ __device__ __forceinline__ void mlp_tile(NetT& net, const float* __restrict__ ob
       for (int r = 0; r < 4; r++) {
         const int row = 4 * (lane >> 4) + r;
         const float v = activate(acc[r] + bias, L.act);
-        if (!last) {
+        if (!last || SAMPLE) {
           Y[row][col] = v;
         } else if (col < L.M && row0 + row < n) {
           act[(size_t)(row0 + row) * act_stride + col] = v;
@@ -201,6 +335,7 @@ __device__ __forceinline__ void mlp_tile(NetT& net, const float* __restrict__ ob
     else layer(buf[cur], buf[cur ^ 1], L, last);
     cur ^= 1;
   }
+  if constexpr (SAMPLE) sample_head(buf[cur], head, act, act_stride, n, row0, tid);
 }
 
 }  // namespace pp3pol
@@ -208,3 +343,5 @@ __device__ __forceinline__ void mlp_tile(NetT& net, const float* __restrict__ ob
 // the device-side network of a policy handle (pp3_policy.hip; C++ linkage, not part of the C ABI)
 const pp3pol::Net* pp3_policy_net(const pp3_policy_t* p);
 int pp3_policy_device(const pp3_policy_t* p);
+// the policy's tanh-Gaussian head, if pp3_policy_set_distribution gave it one
+bool pp3_policy_distribution(const pp3_policy_t* p, float* min_std, float* var_scale);

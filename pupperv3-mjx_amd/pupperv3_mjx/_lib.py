@@ -83,6 +83,14 @@ def load() -> C.CDLL:
     L.pp3_rollout_policy.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.pp3_rollout_policy_timed.argtypes = [vp, vp, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.pp3_policy_last_error.restype = C.c_char_p
+    if hasattr(L, "pp3_policy_sample"):  # (the stochastic head; absent from earlier builds run in kernel A/B)
+        L.pp3_policy_set_distribution.argtypes = [vp, i32, C.c_float, C.c_float]
+        L.pp3_policy_sample.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, vp, vp, vp, vp]
+        L.pp3_rollout_policy_sample.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pp3_rollout_policy_sample_timed.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        for name in ("pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample",
+                     "pp3_rollout_policy_sample_timed"):
+            getattr(L, name).restype = C.c_int
     L.pp3_stream.argtypes = [vp]
     L.pp3_stream.restype = vp
     if hasattr(L, "pp3_event_create"):  # (absent from pre-round-5 builds run in kernel A/B: no host-API step there)
@@ -149,6 +157,7 @@ EXPORTED_SYMBOLS = (
     "pp3_fill_uniform", "pp3_step_timed", "pp3_rollout_timed", "pp3_set_auto_reset", "pp3_set_action_repeat",
     "pp3_policy_create", "pp3_policy_act", "pp3_policy_out_dim", "pp3_policy_destroy", "pp3_policy_last_error",
     "pp3_rollout_policy", "pp3_rollout_policy_timed",
+    "pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample", "pp3_rollout_policy_sample_timed",
     "pp3_stream", "pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy",
     "pp3_set_terrain", "pp3_terrain_slots",
     "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_comm_rank", "pp3_comm_world",

@@ -566,6 +566,9 @@ class PupperV3Env:
         for b in (getattr(self, "_roll_bufs", None) or (0, []))[1]:
             b.free()
         self._roll_bufs = None
+        for b in getattr(self, "_samp_bufs", None) or ():
+            b.free()
+        self._samp_bufs = None
         # free page-locked blocks go with their pools; leased ones are freed when their arrays die
         if getattr(self, "_pin_pool", None) is not None:
             self._pin_pool.retire()
@@ -866,6 +869,72 @@ class PupperV3Env:
         if single:
             traj = {k: v[:, 0] for k, v in traj.items()}
         return self._issue(single), traj
+
+    def rollout_policy_sample(self, state: State, policy, nsteps: int, key) -> Tuple[State, Dict[str, np.ndarray], np.ndarray]:
+        """Brax PPO's data collection (generate_unroll with the training actor in the loop), on
+        device (pp3_rollout_policy_sample): `policy` is an `export.DevicePolicy` made from
+        `export.convert_training_params`; before each of the `nsteps` steps it draws
+        raw ~ Normal(loc, scale) from the env's observation buffer and the env steps on tanh(raw).
+        Key schedule (generate_unroll's): K_0 = `key`; at step t, (cur, next) = split(K_t), the step
+        samples with cur, K_{t+1} = next.  Returns (state after the last step, traj, K_nsteps):
+        pass K_nsteps as the next unroll's key and two chained unrolls equal one long one.
+
+        traj = rollout_policy's {"obs", "action", "reward", "done"} plus "raw_action" [K, N, 12]
+        (the pre-tanh sample, what Brax's learner calls raw_action) and "log_prob" [K, N]
+        (single-env states: without the N axis).
+
+        Assembling PPO's transition t (brax Transition): observation = `state.obs` (the state
+        passed in) for t = 0 and traj["obs"][t - 1] otherwise; action = traj["action"][t];
+        reward = traj["reward"][t]; discount = 1 - traj["done"][t]; next_observation =
+        traj["obs"][t]; extras.policy_extras = {"raw_action": traj["raw_action"][t], "log_prob":
+        traj["log_prob"][t]}.  With auto-reset, traj["obs"][t] of a done step is already the next
+        episode's first observation, as in Brax.  Per-step truncation is not in the trajectory."""
+        self._flush()
+        single = _single_of(state)
+        n, D, K = self.num_envs, self.observation_size, int(nsteps)
+        if K < 1:
+            raise ValueError("nsteps must be >= 1")
+        k_in = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+        k_out = np.zeros(2, dtype=np.uint32)
+        if not self.holds(state):
+            self._write_state(state)
+        blk = self._traj_block(K)  # obs / reward / done straight into page-locked memory (see rollout)
+        bufs = self._rollout_buffers(K, outputs=blk is None)
+        sbuf = self._sample_buffers(K)
+        self._before_launch()
+        outs = blk[1] if blk is not None else (bufs[3].ptr.value, bufs[1].ptr.value, bufs[2].ptr.value)
+        _lib.check(self._L.pp3_rollout_policy_sample(
+            self._h, policy._h, K, k_in.ctypes.data_as(C.c_void_p), k_out.ctypes.data_as(C.c_void_p), bufs[0].ptr,
+            sbuf[0].ptr, sbuf[1].ptr, C.c_void_p(outs[1]), C.c_void_p(outs[2]), C.c_void_p(outs[0]), None))
+        self.synchronize()
+        traj = {"action": np.empty((K, n, _abi.NU), np.float32), "raw_action": np.empty((K, n, _abi.NU), np.float32),
+                "log_prob": np.empty((K, n), np.float32)}
+        bufs[0].download(traj["action"])
+        sbuf[0].download(traj["raw_action"])
+        sbuf[1].download(traj["log_prob"])
+        if blk is not None:
+            traj["obs"], traj["reward"], traj["done"] = self._traj_views(blk[0], K)
+        else:
+            traj.update(obs=np.empty((K, n, D), np.float32), reward=np.empty((K, n), np.float32),
+                        done=np.empty((K, n), np.float32))
+            for b, k in zip(bufs[1:], ("reward", "done", "obs")):
+                b.download(traj[k])
+        if single:
+            traj = {k: v[:, 0] for k, v in traj.items()}
+        return self._issue(single), traj, k_out
+
+    def _sample_buffers(self, K: int) -> list:
+        """Device buffers of rollout_policy_sample(): raw actions and log-probs for K steps; kept and grown."""
+        cur = getattr(self, "_samp_bufs", None)
+        n = self.num_envs
+        sizes = [4 * K * n * _abi.NU, 4 * K * n]
+        if cur is None or any(b.nbytes < s for b, s in zip(cur, sizes)):
+            if cur is not None:
+                for b in cur:
+                    b.free()
+            cur = [_lib.DeviceBuffer(sz, self.device) for sz in sizes]
+            self._samp_bufs = cur
+        return cur
 
     def _traj_block(self, K: int):
         """A page-locked block for a K-step trajectory [obs K x N x 36H | reward K x N | done K x N] and

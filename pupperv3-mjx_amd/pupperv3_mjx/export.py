@@ -8,6 +8,12 @@ Brax PPO's tanh-Gaussian head), per-layer activation names from utils.activation
 meaning of that JSON (what the robot runs); `DevicePolicy` runs it batched on the GPU
 (csrc/pp3_policy.hip, f32 matrix cores) straight from the env's observation buffer, so a
 policy + env rollout never leaves the device.
+
+`convert_training_params` is the training form of the same network: the whole Gaussian head (24
+linear columns) plus the distribution's constants, which is what Brax PPO collects data with
+([ext] brax 0.12.1 training/distribution.py NormalTanhDistribution; quoted from memory, Brax is
+not vendored in the reference).  `sample_forward` is its float64 numpy meaning and
+`DevicePolicy.sample` / `sample_env` / `PupperV3Env.rollout_policy_sample` run it on the GPU.
 """
 from __future__ import annotations
 
@@ -39,6 +45,15 @@ def convert_params(params, activation: str, action_scale: float, kp: float, kd: 
                    maximum_pitch_command: float, maximum_roll_command: float,
                    final_activation: str = "tanh") -> Dict[str, Any]:
     """export.py:13-81.  params = (normalizer with .mean/.std, {"params": {layer: {"kernel", "bias"}}})."""
+    layers, input_size = _dense_layers(params, activation, final_activation, split_head=True)
+    return _policy_dict(layers, input_size, action_scale, kp, kd, default_pose, joint_upper_limits,
+                        joint_lower_limits, use_imu, observation_history, maximum_pitch_command,
+                        maximum_roll_command)
+
+
+def _dense_layers(params, activation: str, final_activation: str, split_head: bool):
+    """export.py:25-58: the dense layers of the exported JSON; split_head cuts the final layer to
+    its first half (the Gaussian head's mean) as the deployment export does."""
     mean, std = _field(params[0], "mean"), _field(params[0], "std")
     params_dict = params[1]["params"]
     layers = []
@@ -51,7 +66,7 @@ def convert_params(params, activation: str, action_scale: float, kp: float, kd: 
         if is_first_layer:
             kernel, bias = fold_in_normalization(A=kernel, b=bias, mean=mean, std=std)
             input_size = kernel.shape[0]
-        if is_final_layer:
+        if is_final_layer and split_head:
             bias, _ = np.split(bias, 2, axis=-1)
             kernel, _ = np.split(kernel, 2, axis=-1)
         layers.append({
@@ -60,6 +75,11 @@ def convert_params(params, activation: str, action_scale: float, kp: float, kd: 
             "shape": [None, len(bias)],
             "weights": [kernel.tolist(), bias.tolist()],
         })
+    return layers, input_size
+
+
+def _policy_dict(layers, input_size, action_scale, kp, kd, default_pose, joint_upper_limits, joint_lower_limits,
+                 use_imu, observation_history, maximum_pitch_command, maximum_roll_command) -> Dict[str, Any]:
     return {
         "use_imu": use_imu,
         "control_orientation": True,
@@ -101,8 +121,66 @@ def policy_forward(policy: Dict[str, Any], obs) -> np.ndarray:
     return h
 
 
+def convert_training_params(params, activation: str, action_scale: float, kp: float, kd: float, default_pose,
+                            joint_upper_limits, joint_lower_limits, use_imu: bool, observation_history: int,
+                            maximum_pitch_command: float, maximum_roll_command: float,
+                            min_std: float = 0.001, var_scale: float = 1.0) -> Dict[str, Any]:
+    """The training form of `convert_params` (same inputs): the final layer keeps all 24 columns
+    (12 means, 12 pre-softplus scales) with "linear" activation, and "distribution" names Brax
+    PPO's NormalTanhDistribution with its constants (Brax's defaults, quoted from memory).
+    tanh of the first 12 outputs is what `convert_params` exports."""
+    layers, input_size = _dense_layers(params, activation, "linear", split_head=False)
+    out = _policy_dict(layers, input_size, action_scale, kp, kd, default_pose, joint_upper_limits,
+                       joint_lower_limits, use_imu, observation_history, maximum_pitch_command,
+                       maximum_roll_command)
+    out["distribution"] = {"type": "normal_tanh", "min_std": float(min_std), "var_scale": float(var_scale)}
+    return out
+
+
+def _softplus(x):
+    return np.maximum(x, 0) + np.log1p(np.exp(-np.abs(x)))
+
+
+def normal_tanh_scale(logits, min_std: float = 0.001, var_scale: float = 1.0):
+    """(loc, scale) of the head: loc = logits[..., :12], scale = (softplus(logits[..., 12:]) + min_std) * var_scale."""
+    logits = np.asarray(logits, dtype=np.float64)
+    loc, s = np.split(logits, 2, axis=-1)
+    return loc, (_softplus(s) + min_std) * var_scale
+
+
+def normal_tanh_log_prob(logits, raw, min_std: float = 0.001, var_scale: float = 1.0) -> np.ndarray:
+    """Brax's NormalTanhDistribution.log_prob(logits, raw_action), float64: the normal's log
+    density of raw minus the tanh's log Jacobian in its stable form 2 (log 2 - raw - softplus(-2 raw))
+    (log(1 - tanh(raw)^2) underflows to log(0) from |raw| ~ 19), summed over the 12 actions."""
+    loc, scale = normal_tanh_scale(logits, min_std, var_scale)
+    raw = np.asarray(raw, dtype=np.float64)
+    zr = (raw - loc) / scale
+    terms = (-0.5 * zr * zr - np.log(scale) - 0.5 * np.log(2 * np.pi)
+             - 2.0 * (np.log(2.0) - raw - _softplus(-2.0 * raw)))
+    return terms.sum(axis=-1)
+
+
+def sample_forward(policy: Dict[str, Any], obs, key, partitionable: bool = True):
+    """Float64 numpy meaning of a training policy's sample: `obs` [n, in] -> (action [n, 12],
+    raw [n, 12], log_prob [n], logits [n, 24]) with the noise rng.normal(key, (n, 12)): row i,
+    column j takes element i * 12 + j of the key's stream."""
+    from . import rng
+    dist = policy["distribution"]
+    if dist["type"] != "normal_tanh":
+        raise ValueError(f"unsupported distribution {dist['type']!r}")
+    logits = policy_forward(policy, np.atleast_2d(np.asarray(obs, dtype=np.float64)))
+    loc, scale = normal_tanh_scale(logits, dist["min_std"], dist["var_scale"])
+    z = rng.normal(key, loc.shape, partitionable).astype(np.float64)
+    raw = loc + scale * z
+    return np.tanh(raw), raw, normal_tanh_log_prob(logits, raw, dist["min_std"], dist["var_scale"]), logits
+
+
+DIST_NORMAL_TANH = 1  # PP3_DIST_NORMAL_TANH
+
+
 class DevicePolicy:
-    """Batched on-device forward of a converted policy dict (pp3_policy_* C ABI)."""
+    """Batched on-device forward of a converted policy dict (pp3_policy_* C ABI).  A dict from
+    `convert_training_params` (with "distribution") also samples: `sample`, `sample_env`."""
 
     def __init__(self, policy: Dict[str, Any], device: int = 0):
         from . import _lib
@@ -136,6 +214,17 @@ class DevicePolicy:
         self.in_dim = in_dim
         self.out_dim = int(outs[-1])
         self.device = int(device)
+        self.distribution = None
+        dist = policy.get("distribution")
+        if dist is not None:
+            if dist.get("type") != "normal_tanh":
+                self.close()
+                raise ValueError(f"unsupported distribution {dist.get('type')!r} (device: 'normal_tanh')")
+            rc = L.pp3_policy_set_distribution(h, DIST_NORMAL_TANH, float(dist["min_std"]), float(dist["var_scale"]))
+            if rc != 0:
+                self.close()
+                raise _lib.PupperHipError(L.pp3_policy_last_error().decode())
+            self.distribution = dict(dist)
 
     def act(self, obs_dev: int, obs_stride: int, n: int, actions_dev: int, action_stride: int, stream=None) -> None:
         rc = self._L.pp3_policy_act(self._h, C.c_void_p(obs_dev), int(obs_stride), int(n), C.c_void_p(actions_dev),
@@ -152,6 +241,28 @@ class DevicePolicy:
         if stream is None:  # order with the env's kernels
             stream = env._L.pp3_stream(env._h)
         self.act(obs_ptr, obs_n, env.num_envs, actions_dev, _abi.NU, stream)
+
+    def sample(self, obs_dev: int, obs_stride: int, n: int, key, actions_dev: int, action_stride: int,
+               raw_dev: int = 0, logp_dev: int = 0, logits_dev: int = 0, partitionable: bool = True, stream=None) -> None:
+        """One tanh-Gaussian sample per row from `key` (uint32[2]): actions [n][12] (row stride
+        action_stride) = tanh(raw); raw [n][12], log_prob [n] and logits [n][24] where given."""
+        k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+        p = lambda v: C.c_void_p(v) if v else None
+        rc = self._L.pp3_policy_sample(self._h, C.c_void_p(obs_dev), int(obs_stride), int(n), k.ctypes.data_as(C.c_void_p),
+                                       int(bool(partitionable)), C.c_void_p(actions_dev), int(action_stride), p(raw_dev),
+                                       p(logp_dev), p(logits_dev), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise self._lib.PupperHipError(self._L.pp3_policy_last_error().decode())
+
+    def sample_env(self, env, key, actions_dev: int, raw_dev: int = 0, logp_dev: int = 0, logits_dev: int = 0,
+                   stream=None) -> None:
+        """actions[N][12] ~ policy(env's current observation buffer), with the env's rng_partitionable."""
+        from . import _abi
+        obs_ptr, obs_n = env.device_field(_abi.F_OBS)
+        if stream is None:  # order with the env's kernels
+            stream = env._L.pp3_stream(env._h)
+        self.sample(obs_ptr, obs_n, env.num_envs, key, actions_dev, _abi.NU, raw_dev, logp_dev, logits_dev,
+                    env._partitionable, stream)
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -13,7 +13,9 @@ requirements.txt:2): ``split`` (environment.py:315,349,506; domain_randomization
   threefry(k, (0, i)) and the 32-bit ``random_bits`` element i = x0 ^ x1 of threefry(k, (0, i));
   ``partitionable=False`` selects the pre-0.5 counter layout instead;
 * ``uniform``: bits >> 9 | 0x3f800000 reinterpreted as f32, minus 1, scaled, max(minval, .);
-  ``bernoulli(p)`` = uniform < p; ``choice(p)`` = searchsorted_left(cumsum(p), cumsum[-1]*(1-u)).
+  ``bernoulli(p)`` = uniform < p; ``choice(p)`` = searchsorted_left(cumsum(p), cumsum[-1]*(1-u));
+* ``normal`` (the PPO actor's noise, not drawn by the env itself): sqrt(2) * erfinv of the
+  uniform on (-1, 1) -- the uniform bit for bit, erfinv to f32 rounding (see ``normal``).
 
 All float arithmetic here is float32 to match JAX with x64 disabled.
 """
@@ -111,6 +113,17 @@ def uniform(key, shape, minval=0.0, maxval=1.0, partitionable: bool = True) -> n
     hi = np.asarray(maxval, dtype=np.float32)
     out = (u * (hi - lo) + lo).astype(np.float32)
     return np.maximum(lo, out).astype(np.float32)
+
+
+def normal(key, shape, partitionable: bool = True) -> np.ndarray:
+    """jax.random.normal restated: sqrt(2) * erfinv(uniform(key, shape, nextafter(-1, 0), 1)), float32.
+    The uniform is jax's bit for bit; erfinv is scipy's in float64 rounded to float32, where XLA
+    evaluates its own f32 erf_inv polynomial, so the result agrees with jax to f32 rounding, not
+    bitwise.  The device head (csrc/pp3_mlp.h sample_head) draws the same stream."""
+    from scipy.special import erfinv  # (local: the package imports without scipy)
+    lo = np.nextafter(np.float32(-1.0), np.float32(0.0))
+    u = uniform(key, shape, lo, 1.0, partitionable)
+    return (np.sqrt(2.0) * erfinv(u.astype(np.float64))).astype(np.float32)
 
 
 def bernoulli(key, p: float, shape=(), partitionable: bool = True) -> np.ndarray:

@@ -107,6 +107,13 @@ class AutoResetEpisodeEnv:
         self._prepare(state)
         return self.env.rollout_policy(state, policy, nsteps)
 
+    def rollout_policy_sample(self, state: State, policy, nsteps: int, key):
+        """K wrapper steps of PPO data collection, the sampling actor in the loop
+        (PupperV3Env.rollout_policy_sample: (state, traj, next_key); its docstring says how a
+        transition is assembled)."""
+        self._prepare(state)
+        return self.env.rollout_policy_sample(state, policy, nsteps, key)
+
     def _prepare(self, state: State) -> None:
         n = self.env.num_envs
         if not self.env.holds(state):

@@ -40,7 +40,7 @@ def classify(prev, nxt):
 
 def main(path, verbose):
     s = open(path).read()
-    a = re.search(r"^_ZN3pp315env_step_kernelILi8ELb1E(?:Li1E)?(?:Lb0E)?EEv\S*:", s, re.M).start()
+    a = re.search(r"^_ZN3pp315env_step_kernelILi8ELb1E(?:Li1E)?(?:Lb0E){0,2}EEv\S*:", s, re.M).start()
     body = [L.strip() for L in s[a:s.index(".Lfunc_end", a)].split("\n")]
     ins = [L for L in body if L and not L.startswith((".", ";")) and not L.endswith(":") and not L.startswith("//")]
     by, pairs = Counter(), Counter()
