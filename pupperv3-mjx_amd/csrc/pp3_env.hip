@@ -71,39 +71,82 @@ union alignas(16) Scratch {
 template <int NC>
 struct alignas(16) Shared {
   static constexpr int NEFC = NFR + NLMAX + 4 * NC;
-  float qpos[20], qvel[20], qws[20], qacc[20], ctrl[12];
-  float st[PP3_S_ACT_BUF];  // head of the state record (latency buffers stay in HBM)
-  // per-env dynamic parameters (domain randomisation)
-  float mass[NB], inertia[NB][3], ipos[NB][3];
-  float fric, kp, kd;
-  int dr_on;
-  float ep[PP3_EP_STRIDE], ep_prev_done;  // auto-reset mode: episode record, previous done
-  float ep_racc;                          // action repeat: the reward summed over this step's earlier repeats
-  // kinematics / dynamics of the current substep (the last one feeds the epilogue)
-  float xpos[NB][3], xquat[NB][4], xaxis[NJ][3];
-  float com[4];
-  float cinert[NB][10];
-  float crb_base[10], cfrc_base[6];  // root-subtree sums (half-wave reductions)
-  float cdof[NV][6];
-  float cvel[NB][6];
-  float M[NV][NV + 1];
-  float gxpos[NROBOT_GEOM][3];
-  float foot_xpos[4][3];
+  // Field order: every array that an operand round reads with 8- or 16-byte loads starts on a
+  // 16-byte boundary (the sizes up to `foot_xpos` are multiples of four words), so rows of an even
+  // stride (cdof, cvel, cinert, Jc; F and cacc in the scratch) are 8-byte aligned for any row index.
+  // The tail (xaxis ... nl) is left at odd word offsets on purpose, behind xaxis' 39 words: its
+  // arrays have odd row strides or are read one word per lane, and where their word pairs were
+  // provably aligned the 8-byte reads' register pairs cost the NC = 16, CULL and policy-rollout
+  // kernels spilled VGPRs (profiles/r08_resource_usage.txt).  dofD's two spare words are the
+  // block's only padding (static_asserts below the struct).
+  alignas(16) float qpos[20], qvel[20], qws[20], qacc[20];
   alignas(16) float search[20];  // (read as b128 words by mrow_dot_reg)
-  float qfrc_smooth[NV], qfrc_act[NV], qacc_smooth[NV], grad[NV], dofD[NV];
+  float ctrl[12];
+  // kinematics / dynamics of the current substep (the last one feeds the epilogue)
+  alignas(16) float xquat[NB][4];
+  float com[4];
+  alignas(16) float cinert[NB][10];
+  alignas(16) float cdof[NV][6];
+  alignas(16) float cvel[NB][6];
   // contacts
-  int ncon, nhit, nl;
+  alignas(16) float Jc[NC][3][NV];
+  float con_G[NC][5];
   int con_pair[NC], con_sup[NC];
   uint32_t con_dm[NC][2];  // dof masks of the contact's two bodies
   float con_dist[NC], con_mu[NC];
-  float con_G[NC][5];
-  float Jc[NC][3][NV];
   // constraint rows
   int lim_dof[NLMAX];
   float lim_sgn[NLMAX];
   float efc_D[NEFC], efc_R[NEFC], efc_aref[NEFC], efc_force[NEFC];
+  float gxpos[NROBOT_GEOM][3];
+  float foot_xpos[4][3];
+  // the tail, at odd word offsets (see above)
+  float xaxis[NJ][3];
+  float cfrc_base[6];  // root-subtree sums (half-wave reductions)
+  float xpos[NB][3];
+  float crb_base[10];
+  float st[PP3_S_ACT_BUF];  // head of the state record (latency buffers stay in HBM)
+  float M[NV][NV + 1];
+  // per-env dynamic parameters (domain randomisation)
+  float ipos[NB][3], mass[NB], inertia[NB][3];
+  float grad[NV], qacc_smooth[NV], qfrc_smooth[NV], qfrc_act[NV];
+  float fric, kp, kd;
+  int dr_on;
+  float ep[PP3_EP_STRIDE], ep_prev_done;  // auto-reset mode: episode record, previous done
+  float ep_racc;                          // action repeat: the reward summed over this step's earlier repeats
+  int ncon, nhit, nl;
+  alignas(16) float dofD[NV];
   Scratch<NC> x;
 };
+// The env block does not grow: two blocks per wave, two waves per SIMD, and the policy rollout's
+// sixteen blocks fill a workgroup's LDS to within a few hundred bytes.
+static_assert(sizeof(Shared<8>) <= 9872 && sizeof(Shared<16>) <= 12848, "the env block must not grow");
+// the words of the fields in front of the scratch union, summed field by field (update with the
+// struct): the block holds them, dofD's two spare words and the union, nothing else
+template <int NC>
+constexpr int shared_field_words() {
+  return 4 * 20 + 20 + 12                                 // qpos qvel qws qacc, search, ctrl
+         + NB * 4 + 4 + NB * 10 + NV * 6 + NB * 6         // xquat com cinert cdof cvel
+         + NC * 3 * NV + NC * 5 + 2 * NC + 2 * NC + 2 * NC  // Jc con_G, con_pair con_sup, con_dm, con_dist con_mu
+         + 2 * NLMAX + 4 * Shared<NC>::NEFC               // lim_dof lim_sgn, efc_D efc_R efc_aref efc_force
+         + NROBOT_GEOM * 3 + 4 * 3                        // gxpos foot_xpos
+         + NJ * 3 + 6 + NB * 3 + 10 + PP3_S_ACT_BUF + NV * (NV + 1)  // xaxis cfrc_base xpos crb_base st M
+         + NB * 3 + NB + NB * 3 + 4 * NV                  // ipos mass inertia, grad qacc_smooth qfrc_smooth qfrc_act
+         + 4 + PP3_EP_STRIDE + 2 + 3                      // fric kp kd dr_on, ep ep_prev_done ep_racc, ncon nhit nl
+         + NV;                                            // dofD
+}
+static_assert(sizeof(Shared<8>) == (shared_field_words<8>() + 2) * 4 + sizeof(Scratch<8>) &&
+              sizeof(Shared<16>) == (shared_field_words<16>() + 2) * 4 + sizeof(Scratch<16>),
+              "Shared: padding beyond dofD's two words (a new field: add it to shared_field_words and keep the groups' sizes)");
+template <int NC>
+constexpr bool shared_operands_aligned() {
+  return offsetof(Shared<NC>, search) % 16 == 0 && offsetof(Shared<NC>, xquat) % 16 == 0 &&
+         offsetof(Shared<NC>, cinert) % 16 == 0 && offsetof(Shared<NC>, cdof) % 16 == 0 &&
+         offsetof(Shared<NC>, cvel) % 16 == 0 && offsetof(Shared<NC>, Jc) % 16 == 0 &&
+         offsetof(Shared<NC>, dofD) % 16 == 0 && offsetof(Shared<NC>, x) % 16 == 0;
+}
+static_assert(shared_operands_aligned<8>() && shared_operands_aligned<16>(), "Shared: aligned operand arrays");
+static_assert(offsetof(Shared<8>, cfrc_base) % 8 == 4 && offsetof(Shared<8>, nl) % 8 == 4, "Shared: the tail sits at odd word offsets");
 
 // A workgroup is ONE wave and LDS executes a wave's instructions in issue order, so a lane's
 // LDS store is visible to every later LDS load of the same wave: phase boundaries only need to
