@@ -39,6 +39,13 @@ int32_t pp3_rollout_policy_fused(const pp3_env_t* e);
  * PP3_NO_CULL=1 at creation), -1 = null handle.  The cull is exact (tests/test_gpu_cull.py). */
 int32_t pp3_narrow_cull(const pp3_env_t* e);
 
+/* The size caps of the env_step_kernel instantiation a step launch of env `e` takes: history cap
+ * << 8 | latency-row cap.  2 << 8 | 2 when the contact cap is 8 and observation_history and both
+ * latency distributions have at most 2 entries (the kernels unrolled over those extents), 16 << 8 | 8
+ * (the ABI's limits) otherwise; -1 = null handle.  `fused`: a pp3_rollout launch (1) or a pp3_step
+ * launch (0); `policy`: 1 for a launch of one of the two policy rollouts, 0 otherwise. */
+int32_t pp3_diag_step_variant(const pp3_env_t* e, int32_t fused, int32_t policy);
+
 #ifdef __cplusplus
 }
 #endif

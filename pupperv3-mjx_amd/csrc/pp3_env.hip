@@ -38,6 +38,19 @@ typedef __attribute__((address_space(4))) const DevModel GModel;  // DevModel: r
 typedef __attribute__((address_space(4))) const float GFloat;
 constexpr int HMAX = 16;    // observation_history limit
 constexpr int OBS_MOVE = (PP3_OBS_DIM * (HMAX - 1) + HW - 1) / HW;
+// Size caps a step kernel is compiled for: observation_history <= H and both latency rows <= LAG.
+// The history move, the lag rows and the IMU stash are unrolled over these extents (the runtime
+// sizes guard inside them), so every slot of the cap costs its compare, EXEC region and branch
+// whether the model uses it or not.  Caps<HMAX, PP3_MAX_LAG> is the ABI's limit; the launches pick
+// Caps<2, 2> when the model fits (small_caps below).
+template <int HCAP, int LAGCAP>
+struct Caps {
+  static_assert(HCAP >= 1 && HCAP <= HMAX && LAGCAP >= 1 && LAGCAP <= PP3_MAX_LAG, "caps within the ABI's limits");
+  static constexpr int H = HCAP, LAG = LAGCAP;
+  static constexpr int MOVE = (PP3_OBS_DIM * (HCAP - 1) + HW - 1) / HW;  // history words per lane
+};
+using CapsMax = Caps<HMAX, PP3_MAX_LAG>;
+using CapsSmall = Caps<2, 2>;
 constexpr int NROBOT_GEOM = 8;  // collidable spheres on moving bodies (LDS table)
 constexpr int NHIT = 64;        // contact-overflow ranking window (hits kept for ranking)
 constexpr float CULL_SLACK = 0.05f;  // collision's cached near-box mask: re-tested after body 1 moves this far (m)
@@ -1455,22 +1468,23 @@ __device__ __forceinline__ void hess_acc(float (&a)[NV], const float (&J)[3][NV]
 }
 
 // index drawn by jax.random.choice(p) from u = uniform(key): searchsorted_left(cumsum(p), cumsum[-1]*(1-u))
-// (n <= PP3_MAX_LAG; unrolled over the cap so the wave-uniform dist reads are one scalar load)
+// (n <= LAGCAP <= PP3_MAX_LAG; unrolled over the cap so the wave-uniform dist reads are one scalar load)
+template <int LAGCAP = PP3_MAX_LAG>
 __device__ __forceinline__ int choice_from_uniform(const GFloat* dist, int n, float u) {
   // the whole (fixed-size) table first: one batch of scalar loads and one wait, not a load and a
   // wait behind every `i < n` branch (16 serial round trips per call)
-  float d[PP3_MAX_LAG];
+  float d[LAGCAP];
 #pragma unroll
-  for (int i = 0; i < PP3_MAX_LAG; i++) d[i] = dist[i];
+  for (int i = 0; i < LAGCAP; i++) d[i] = dist[i];
   float total = 0.0f;
 #pragma unroll
-  for (int i = 0; i < PP3_MAX_LAG; i++)
+  for (int i = 0; i < LAGCAP; i++)
     if (i < n) total += d[i];
   const float r = total * (1.0f - u);
   float acc = 0.0f;
   int li = 0;
 #pragma unroll
-  for (int i = 0; i < PP3_MAX_LAG; i++)
+  for (int i = 0; i < LAGCAP; i++)
     if (i < n) {
       acc += d[i];
       li += (acc < r) ? 1 : 0;
@@ -2254,13 +2268,14 @@ __device__ __forceinline__ void load_params(Shared<NC>& s, const DevModel& m, co
 
 // sample_lagged_value on one buffer row in HBM (utils.py:34-69): push `v` to the front of
 // row[0..n), return the value now at column li.  Register-staged (read all, then write).
+template <int LAGCAP = PP3_MAX_LAG>
 __device__ __forceinline__ float push_lagged(float* row, int n, float v, int li, bool store) {
-  float old[PP3_MAX_LAG];
+  float old[LAGCAP];
 #pragma unroll
-  for (int q = 0; q < PP3_MAX_LAG; q++) old[q] = q < n ? row[q] : 0.0f;
+  for (int q = 0; q < LAGCAP; q++) old[q] = q < n ? row[q] : 0.0f;
   float out = v;
 #pragma unroll
-  for (int q = 0; q < PP3_MAX_LAG; q++) {
+  for (int q = 0; q < LAGCAP; q++) {
     const float nv = q == 0 ? v : old[q - 1];
     if (store && q < n) row[q] = nv;
     out = (q == li) ? nv : out;
@@ -2269,10 +2284,11 @@ __device__ __forceinline__ float push_lagged(float* row, int n, float v, int li,
 }
 
 // push_lagged with the row's old values already loaded (prefetched at kernel start)
+template <int LAGCAP = PP3_MAX_LAG>
 __device__ __forceinline__ float push_lagged_pre(float* row, int n, float v, int li, bool store, const float* old) {
   float out = v;
 #pragma unroll
-  for (int q = 0; q < PP3_MAX_LAG; q++) {
+  for (int q = 0; q < LAGCAP; q++) {
     const float nv = q == 0 ? v : old[q - 1];
     if (store && q < n) row[q] = nv;
     out = (q == li) ? nv : out;
@@ -2324,8 +2340,9 @@ __device__ __forceinline__ void sample_orientation(const DevModel& m, Key rng, f
 }
 
 // _get_obs (environment.py:485-543): consumes the st rng, pushes the IMU buffer (HBM row
-// gimu = [6][Li]), writes s.x.e.o[36]
-template <int NC>
+// gimu = [6][Li]), writes s.x.e.o[36].  LAGCAP >= m.Li: the slots of a row touched (imu_stash keeps
+// its stride of PP3_MAX_LAG)
+template <int NC, int LAGCAP = PP3_MAX_LAG>
 __device__ __forceinline__ void get_obs(Shared<NC>& s, const DevModel& m, float* gimu, int l, int h, float pose16, bool store,
                                         const float* imu_stash PROF_PARAM) {
   const int part = m.partitionable;
@@ -2357,15 +2374,15 @@ __device__ __forceinline__ void get_obs(Shared<NC>& s, const DevModel& m, float*
     for (int k = 0; k < 3; k++) g[k] += s.x.e.u[3 + k];
     const float gn = sqrtf(dot3(g, g));
     const float v = l < 3 ? angl[l] + s.x.e.u[l] : g[l - 3] / gn;
-    const int li = choice_from_uniform((const GFloat*)m.imu_lat_dist, m.Li, s.x.e.u[30]);
+    const int li = choice_from_uniform<LAGCAP>((const GFloat*)m.imu_lat_dist, m.Li, s.x.e.u[30]);
     float lagged;
     if (imu_stash) {  // the row's old values were fetched at kernel start (one memory round trip)
-      float old[PP3_MAX_LAG];
+      float old[LAGCAP];
 #pragma unroll
-      for (int q = 0; q < PP3_MAX_LAG; q++) old[q] = imu_stash[PP3_MAX_LAG * l + q];
-      lagged = push_lagged_pre(gimu + l * m.Li, m.Li, v, li, store, old);
+      for (int q = 0; q < LAGCAP; q++) old[q] = imu_stash[PP3_MAX_LAG * l + q];
+      lagged = push_lagged_pre<LAGCAP>(gimu + l * m.Li, m.Li, v, li, store, old);
     } else {
-      lagged = push_lagged(gimu + l * m.Li, m.Li, v, li, store);
+      lagged = push_lagged<LAGCAP>(gimu + l * m.Li, m.Li, v, li, store);
     }
     s.x.e.o[l] = fminf(fmaxf(lagged, -100.0f), 100.0f);
   }
@@ -2701,7 +2718,9 @@ __device__ __noinline__ void policy_mlp_sample(GSArgs* ga, LdsObsTile* in, int i
 // sphere-box cull of collision() compiled in; the flat model's code is the same without it
 // SAMPLE: the policy rollout with the stochastic head (its own instantiation and argument record:
 // the others compile to what they were without it)
-template <int NC, bool FUSED, int NWV = 1, bool CULL = false, bool SAMPLE = false>
+// CAPS: the history and lag extents the step's shell is unrolled over (Caps above); the launches
+// take CapsSmall when the model fits it and the contact cap is 8, CapsMax otherwise
+template <int NC, bool FUSED, int NWV = 1, bool CULL = false, bool SAMPLE = false, class CAPS = CapsMax>
 __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
     typename std::conditional<SAMPLE, SamplePolicyStepArgs,
                               typename std::conditional<(NWV > 1), PolicyStepArgs, StepArgs>::type>::type a_arg) {
@@ -2818,12 +2837,12 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
   float* oo = a.obs_out + obs_base;
   // fused steps after the first: the env's LDS block still holds what this wave left in it
   const bool carry = FUSED && NWV == 1 && it > 0;
-  float arow[PP3_MAX_LAG], irow[PP3_MAX_LAG], act_in = 0.0f;
+  float arow[CAPS::LAG], irow[CAPS::LAG], act_in = 0.0f;
   {
     const float* ar = gst + PP3_S_ACT_BUF + (l < NU ? l : 0) * m.La;
     const float* ir = gst + m.imu_off + (l < 6 ? l : 0) * m.Li;
 #pragma unroll
-    for (int q = 0; q < PP3_MAX_LAG; q++) {
+    for (int q = 0; q < CAPS::LAG; q++) {
       arow[q] = (l < NU && q < m.La) ? ar[q] : 0.0f;
       irow[q] = (l < 6 && q < m.Li) ? ir[q] : 0.0f;
     }
@@ -2837,9 +2856,9 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
   const int nmove = PP3_OBS_DIM * (m.H - 1);
   // carry with H = 2: the history frame is the previous step's newest observation, still in LDS
   const bool hist_lds = carry && nmove == PP3_OBS_DIM;
-  float tmp[OBS_MOVE];
+  float tmp[CAPS::MOVE > 0 ? CAPS::MOVE : 1];
 #pragma unroll
-  for (int t = 0; t < OBS_MOVE; t++) {
+  for (int t = 0; t < CAPS::MOVE; t++) {
     const int k = l + HW * t;
     if (hist_lds) tmp[t] = (k < PP3_OBS_DIM) ? s.x.e.o[k < PP3_OBS_DIM ? k : 0] : 0.0f;
     else tmp[t] = (k < nmove) ? oi[k] : 0.0f;
@@ -2862,7 +2881,7 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
   if (!hist_lds) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (own)
 #pragma unroll
-    for (int t = 0; t < OBS_MOVE; t++)
+    for (int t = 0; t < CAPS::MOVE; t++)
       if (l + HW * t < nmove) {
         oo[PP3_OBS_DIM + l + HW * t] = tmp[t];
         if constexpr (NWV > 1)
@@ -2888,7 +2907,7 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
   }
   const float bern = hb(u, 2, h) < m.kick_p ? 1.0f : 0.0f;
   const float kick0 = hb(u, 0, h) * m.kick_vel * bern, kick1 = hb(u, 1, h) * m.kick_vel * bern;
-  const int li = choice_from_uniform((const GFloat*)m.lat_dist, m.La, hb(u, 3, h));
+  const int li = choice_from_uniform<CAPS::LAG>((const GFloat*)m.lat_dist, m.La, hb(u, 3, h));
   if (l == 0) {
     s.qvel[0] += kick0;
     s.qvel[1] += kick1;
@@ -2898,7 +2917,7 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
     s.st[PP3_S_RNG + 1] = __uint_as_float(k_new.b);
   }
   if (l < NU) {
-    const float lagged = push_lagged_pre(gst + PP3_S_ACT_BUF + l * m.La, m.La, act_in, li, own, arow);
+    const float lagged = push_lagged_pre<CAPS::LAG>(gst + PP3_S_ACT_BUF + l * m.La, m.La, act_in, li, own, arow);
     const float t = re.f[LE_POSE] + lagged * m.action_scale;
     s.ctrl[l] = fminf(fmaxf(t, re.f[LE_JLO]), re.f[LE_JHI]);
   }
@@ -2908,7 +2927,7 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
   float* imu_stash = s.st + PP3_S_QPOS;
   if (l < 6)
 #pragma unroll
-    for (int q = 0; q < PP3_MAX_LAG; q++) imu_stash[PP3_MAX_LAG * l + q] = irow[q];
+    for (int q = 0; q < CAPS::LAG; q++) imu_stash[PP3_MAX_LAG * l + q] = irow[q];
   SYNC();
   PHASE(10);
   // ---- physics: n_frames x mj_step (environment.py:366) ----
@@ -2958,7 +2977,7 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
   const DevModel& m = *(const DevModel*)mq;
   const LaneRec<2> re = fetch_rec(m.lane_env, l);  // this lane's env constants (one round trip)
   // ---- observation (history already shifted in the prologue) ----
-  get_obs(s, m, gst + m.imu_off, l, h, re.f[LE_POSE16], own, imu_stash PROF_ARG);
+  get_obs<NC, CAPS::LAG>(s, m, gst + m.imu_off, l, h, re.f[LE_POSE16], own, imu_stash PROF_ARG);
   {
     if (own)
       for (int k = l; k < PP3_OBS_DIM; k += HW) {
@@ -3376,6 +3395,7 @@ struct pp3_env {
   int N;
   int stride;
   int H;
+  int La, Li;  // latency rows' lengths (with H: which size caps the step kernels are launched with)
   hipStream_t stream;
   DevModel* dmodel;
   float* state;
@@ -3922,6 +3942,17 @@ static int build_devmodel(const pp3_model_t* mm, const pp3_env_config_t* c, DevM
   return PP3_OK;
 }
 
+// The step launches of env e take the Caps<2, 2> instantiations (contact cap 8 only: the shipped
+// model's shapes) when its history and both latency rows fit them, the ABI-limit ones otherwise.
+static bool small_caps(const pp3_env_t* e) { return e->nc == 8 && e->H <= CapsSmall::H && e->La <= CapsSmall::LAG && e->Li <= CapsSmall::LAG; }
+
+// launch env_step_kernel<8, FUSED, NWV, CULL, SAMPLE> with the caps of env e
+template <bool FUSED, int NWV, bool CULL, bool SAMPLE, class Args>
+static void launch_nc8(const pp3_env_t* e, dim3 grid, dim3 block, hipStream_t st, const Args& a) {
+  if (small_caps(e)) hipLaunchKernelGGL((env_step_kernel<8, FUSED, NWV, CULL, SAMPLE, CapsSmall>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((env_step_kernel<8, FUSED, NWV, CULL, SAMPLE>), grid, block, 0, st, a);
+}
+
 extern "C" {
 
 int pp3_abi_version(void) { return PP3_ABI_VERSION; }
@@ -3964,6 +3995,8 @@ int pp3_create(const pp3_model_t* model, const pp3_env_config_t* cfg, int32_t nu
   e->N = num_envs;
   e->stride = hm.stride;
   e->H = hm.H;
+  e->La = hm.La;
+  e->Li = hm.Li;
   e->partitionable = hm.partitionable;
   e->nbox = hm.nbox;
   e->cull = hm.cull_on;
@@ -4100,17 +4133,17 @@ static int launch_steps(pp3_env_t* e, const float* actions_dev, int64_t action_s
     for (a.phase = 0; a.phase < a.repeat; a.phase++) {  // action_repeat: the same action, k launches
       if (e->cull) {
         if (fused) {
-          if (e->nc == 8) hipLaunchKernelGGL((env_step_kernel<8, true, 1, true>), grid, block, 0, st, a);
+          if (e->nc == 8) launch_nc8<true, 1, true, false>(e, grid, block, st, a);
           else hipLaunchKernelGGL((env_step_kernel<16, true, 1, true>), grid, block, 0, st, a);
         } else {
-          if (e->nc == 8) hipLaunchKernelGGL((env_step_kernel<8, false, 1, true>), grid, block, 0, st, a);
+          if (e->nc == 8) launch_nc8<false, 1, true, false>(e, grid, block, st, a);
           else hipLaunchKernelGGL((env_step_kernel<16, false, 1, true>), grid, block, 0, st, a);
         }
       } else if (fused) {
-        if (e->nc == 8) hipLaunchKernelGGL((env_step_kernel<8, true>), grid, block, 0, st, a);
+        if (e->nc == 8) launch_nc8<true, 1, false, false>(e, grid, block, st, a);
         else hipLaunchKernelGGL((env_step_kernel<16, true>), grid, block, 0, st, a);
       } else {
-        if (e->nc == 8) hipLaunchKernelGGL((env_step_kernel<8, false>), grid, block, 0, st, a);
+        if (e->nc == 8) launch_nc8<false, 1, false, false>(e, grid, block, st, a);
         else hipLaunchKernelGGL((env_step_kernel<16, false>), grid, block, 0, st, a);
       }
       HIPCHK(hipGetLastError());
@@ -4148,6 +4181,14 @@ static bool policy_rollout_fused(const pp3_env_t* e) {
 
 int32_t pp3_rollout_policy_fused(const pp3_env_t* e) { return e ? (policy_rollout_fused(e) ? 1 : 0) : -1; }
 int32_t pp3_narrow_cull(const pp3_env_t* e) { return e ? (e->cull ? 1 : 0) : -1; }
+// (every launch kind decides by small_caps alone today: a fused rollout, a single step, the policy
+// rollouts' fused kernel and their per-step launches)
+int32_t pp3_diag_step_variant(const pp3_env_t* e, int32_t fused, int32_t policy) {
+  (void)fused;
+  (void)policy;
+  if (!e) return -1;
+  return small_caps(e) ? (CapsSmall::H << 8 | CapsSmall::LAG) : (CapsMax::H << 8 | CapsMax::LAG);
+}
 
 int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float* actions_dev, float* reward_dev,
                        float* done_dev, float* obs_dev, void* stream) {
@@ -4192,8 +4233,8 @@ int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float
     pa.act = actions_dev;
     pa.net = *pp3_policy_net(policy);
     const dim3 grid((e->N + pp3pol::TILE - 1) / pp3pol::TILE), block(WAVE * pp3pol::NWAVE);
-    if (e->cull) hipLaunchKernelGGL((env_step_kernel<8, true, pp3pol::NWAVE, true>), grid, block, 0, st, pa);
-    else hipLaunchKernelGGL((env_step_kernel<8, true, pp3pol::NWAVE>), grid, block, 0, st, pa);
+    if (e->cull) launch_nc8<true, pp3pol::NWAVE, true, false>(e, grid, block, st, pa);
+    else launch_nc8<true, pp3pol::NWAVE, false, false>(e, grid, block, st, pa);
     HIPCHK(hipGetLastError());
     return PP3_OK;
   }
@@ -4310,8 +4351,8 @@ int pp3_rollout_policy_sample(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps
     sa.min_std = min_std;
     sa.var_scale = var_scale;
     const dim3 grid((e->N + pp3pol::TILE - 1) / pp3pol::TILE), block(WAVE * pp3pol::NWAVE);
-    if (e->cull) hipLaunchKernelGGL((env_step_kernel<8, true, pp3pol::NWAVE, true, true>), grid, block, 0, st, sa);
-    else hipLaunchKernelGGL((env_step_kernel<8, true, pp3pol::NWAVE, false, true>), grid, block, 0, st, sa);
+    if (e->cull) launch_nc8<true, pp3pol::NWAVE, true, true>(e, grid, block, st, sa);
+    else launch_nc8<true, pp3pol::NWAVE, false, true>(e, grid, block, st, sa);
     HIPCHK(hipGetLastError());
     Key kt = k0;  // K_nsteps: the chain's `next` halves (host threefry)
     for (int t = 0; t < nsteps; t++) kt = host_split2(kt, 1, part);

@@ -3,7 +3,8 @@
   python tools/pmc_census.py <dir> --steps-per-launch 200 [--out profiles/<name>.json] [--against <other.json>]
 
 <dir> holds one sub-directory per `rocprofv3 --pmc ...` pass of the same bench command (any names);
-every counter of the LAST dispatch of env_step_kernel<8, true, 1, false, false> (the timed fused launch)
+every counter of the LAST dispatch of env_step_kernel<8, true, 1, false, false, ...> (the timed fused launch,
+whichever size caps it was compiled for)
 is divided by that pass's SQ_WAVES and by the launch's step count: figures per wave and env step
 (a wave runs two envs).  Counters collected in more than one pass are averaged.  --against prints
 the difference to an earlier census.
@@ -15,7 +16,7 @@ import os
 import sys
 from collections import defaultdict
 
-KERNEL = "env_step_kernel<8, true, 1, false, false>"
+KERNEL = "env_step_kernel<8, true, 1, false, false"  # (a prefix: the size caps follow from round 9 on)
 
 
 def _arg(name, default=None):

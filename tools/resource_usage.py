@@ -65,11 +65,11 @@ def main(extra):
             body["scr_st"] += 1
     names = demangle(list(funcs))
     print(f"# src_sha16 {bench.kernel_source_sha16()}  flags {' '.join(extra) or '(product)'}")
-    print(f"# {'function':62s} {'VGPR':>4s} {'SGPR':>4s} {'spill s/v':>9s} {'scratch':>7s} {'LDS B':>6s} {'occ':>3s} {'scr ld/st':>9s}")
+    print(f"# {'function':82s} {'VGPR':>4s} {'SGPR':>4s} {'spill s/v':>9s} {'scratch':>7s} {'LDS B':>6s} {'occ':>3s} {'scr ld/st':>9s}")
     for n, f in funcs.items():
         if "vgpr" not in f:
             continue
-        print(f"  {names.get(n, n)[:62]:62s} {f['vgpr']:4d} {f.get('sgpr', 0):4d} {f.get('sgpr_spill', 0):4d}/{f.get('vgpr_spill', 0):<4d}"
+        print(f"  {names.get(n, n)[:82]:82s} {f['vgpr']:4d} {f.get('sgpr', 0):4d} {f.get('sgpr_spill', 0):4d}/{f.get('vgpr_spill', 0):<4d}"
               f" {f.get('scratch', 0):7d} {f.get('lds', 0):6d} {f.get('occ', 0):3d} {f.get('scr_ld', 0):4d}/{f.get('scr_st', 0):<4d}")
 
 
