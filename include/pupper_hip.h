@@ -551,6 +551,42 @@ int pp3_rollout_policy_sample_timed(pp3_env_t* env, pp3_policy_t* policy, int32_
                                     uint32_t* key_out, float* actions_dev, float* raw_dev, float* logp_dev,
                                     float* reward_dev, float* done_dev, float* obs_dev, float* kernel_ms_total);
 
+/* ---- PPO batch: truncation rows and value targets (additive; PP3_ABI_VERSION stays 2) ----
+ * With the sampling actor above and a 1-column critic run through pp3_policy_act
+ * (pupperv3_mjx/export.py convert_value_params), these give a learner everything brax's
+ * compute_ppo_loss consumes without the trajectory leaving the device
+ * (PupperV3Env.collect_ppo). */
+/* EpisodeWrapper's info['truncation'] per step ([ext] brax 0.12.1 envs/wrappers/training.py):
+ * after this call every pp3_rollout / pp3_rollout_policy / pp3_rollout_policy_sample (and their
+ * _timed forms) of nsteps <= max_steps also writes trunc_dev f32[nsteps][N], row t = the value
+ * PP3_EP_TRUNCATION holds after wrapper step t (all zeros when auto-reset is off).  nsteps >
+ * max_steps: PP3_ERR_ARG before anything is launched.  trunc_dev NULL (the state after
+ * pp3_create) turns it off.  The buffer stays the caller's; pp3_step never writes it. */
+int pp3_set_truncation_trajectory(pp3_env_t* env, float* trunc_dev, int32_t max_steps);
+/* Brax PPO's generalised advantage estimation ([ext] brax 0.12.1 training/agents/ppo/losses.py
+ * compute_gae as compute_ppo_loss calls it; restated from memory, the recurrence below is the
+ * contract).  All device pointers; trajectory arrays [nsteps][N] with row stride `row_stride`
+ * floats (>= N); bootstrap f32[N]; outputs vs (the value targets) and adv [nsteps][N], same
+ * stride.  In-place is not supported (PP3_ERR_ARG if an output aliases an input).  f32, every
+ * *, + and - rounded on its own in exactly this association (no fused multiply-add):
+ *   for t = nsteps-1 .. 0, per env, with vnext = bootstrap and acc = 0 before the loop:
+ *     tm    = 1 - truncation[t]
+ *     term  = done[t] * tm                    (1 - discount_t)(1 - truncation_t), discount_t = 1 - done_t
+ *     g     = discount * (1 - term)
+ *     r     = reward[t] * reward_scaling
+ *     delta = ((r + g * vnext) - values[t]) * tm
+ *     acc   = delta + (((g * tm) * lambda) * acc)
+ *     vs[t] = acc + values[t]
+ *     vnext = values[t]
+ *   then adv[t] = ((r_t + g_t * vs[t+1]) - values[t]) * tm_t, with vs[nsteps] = bootstrap.
+ * One kernel on `stream` (NULL = default stream) of `device`, one lane per env; PP3_ERR_ARG
+ * (nothing launched) on a null pointer, nsteps < 1, n < 1, row_stride < n or a non-finite
+ * discount / lambda / reward_scaling.  Its own errors via pp3_ppo_last_error(). */
+int pp3_gae(int32_t device, int32_t nsteps, int32_t n, int64_t row_stride, const float* reward,
+            const float* done, const float* truncation, const float* values, const float* bootstrap,
+            float discount, float lambda, float reward_scaling, float* vs, float* adv, void* stream);
+const char* pp3_ppo_last_error(void);
+
 /* ---------------------------------------------------------------------------------------
  * Multi-GPU (no reference code: the reference runs one process per device under
  * Brax PPO's pmap, [ext] brax 0.12.1 brax/training/agents/ppo/train.py, where the env batch is

@@ -2608,6 +2608,8 @@ struct StepArgs {
   float* traj_reward;    // fused rollout outputs, each optional: [nsteps][N]
   float* traj_done;      // [nsteps][N]
   float* traj_obs;       // [nsteps][N][36H]
+  float* traj_trunc;     // [nsteps][N] EpisodeWrapper's truncation per step (pp3_set_truncation_trajectory);
+                         // FUSED kernels only (after a single-step launch: trunc_row_kernel)
 };
 
 // The fused policy rollout (pp3_rollout_policy): the env step kernel with eight waves = 16 envs
@@ -3171,6 +3173,17 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
     if (TG && (!a.episode || last)) {
       if (o_treward) o_treward[(size_t)it * a.N + env] = rout;
       if (o_tdone) o_tdone[(size_t)it * a.N + env] = done_out ? 1.0f : 0.0f;
+      // info['truncation'] = trunc_hit && !isdone, from what is live here (done_out = isdone ||
+      // trunc_hit; without auto-reset done_out = isdone: 0) instead of a flag carried down from
+      // the episode block.  Its pointer is read here, not with the others above: held from there
+      // it cost four to five more SGPR spills per instantiation.  Fused kernels only: the
+      // single-step kernel holds its by-value arguments from the top and spilled likewise, so
+      // its launches are followed by trunc_row_kernel instead (launch_steps) and it compiles to
+      // the code it was.
+      if constexpr (FUSED) {
+        float* const o_ttrunc = a.traj_trunc;
+        if (o_ttrunc) o_ttrunc[(size_t)it * a.N + env] = (done_out && !isdone) ? 1.0f : 0.0f;
+      }
     }
     o_metrics[(size_t)env * PP3_NMETRIC] =
         sqrtf(s.xpos[tb][0] * s.xpos[tb][0] + s.xpos[tb][1] * s.xpos[tb][1] + s.xpos[tb][2] * s.xpos[tb][2]);
@@ -3418,6 +3431,8 @@ struct pp3_env {
   int nbox;        // world box-geom slots in the model
   int cull;        // DevModel::cull_on: steps launch env_step_kernel<..., CULL = true>
   int partitionable;  // the config's rng_partitionable (the sampled policy rollout's host key chain)
+  float* traj_trunc;  // pp3_set_truncation_trajectory: the rollouts' truncation rows (caller's buffer) or null
+  int trunc_steps;    // its capacity in steps
   hipEvent_t ev0, ev1;
 };
 
@@ -4096,8 +4111,23 @@ static const bool g_policy_unfused = [] {
   return v && v[0] == '1';
 }();
 
+// pp3_set_truncation_trajectory: a rollout longer than the registered rows is refused before any launch
+static bool trunc_over(const pp3_env_t* e, int nsteps) { return e->traj_trunc && nsteps > e->trunc_steps; }
+static std::string trunc_over_msg(const pp3_env_t* e, int nsteps) {
+  return "nsteps " + std::to_string(nsteps) + " exceeds the truncation trajectory's max_steps " +
+         std::to_string(e->trunc_steps) + " (pp3_set_truncation_trajectory)";
+}
+
+// A single-step launch's truncation row (the single-step kernel does not write it: see its store of
+// the trajectory rows): out[i] = the episode record's flag after the step, 0 without auto-reset
+__global__ void trunc_row_kernel(const float* __restrict__ episode, float* __restrict__ out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = episode ? episode[(size_t)i * PP3_EP_STRIDE + PP3_EP_TRUNCATION] : 0.0f;
+}
+
 static int launch_steps(pp3_env_t* e, const float* actions_dev, int64_t action_stride, int32_t nsteps,
-                        float* traj_reward, float* traj_done, float* traj_obs, bool fused, void* stream) {
+                        float* traj_reward, float* traj_done, float* traj_obs, float* traj_trunc, bool fused,
+                        void* stream) {
   HIPCHK(hipSetDevice(e->device));
   StepArgs a;
   a.m = e->dmodel;
@@ -4130,6 +4160,8 @@ static int launch_steps(pp3_env_t* e, const float* actions_dev, int64_t action_s
     a.traj_reward = traj_reward ? traj_reward + (one_launch ? 0 : (size_t)t * e->N) : nullptr;
     a.traj_done = traj_done ? traj_done + (one_launch ? 0 : (size_t)t * e->N) : nullptr;
     a.traj_obs = traj_obs ? traj_obs + (one_launch ? 0 : (size_t)t * on) : nullptr;
+    float* const trunc_row = traj_trunc ? traj_trunc + (one_launch ? 0 : (size_t)t * e->N) : nullptr;
+    a.traj_trunc = fused ? trunc_row : nullptr;
     for (a.phase = 0; a.phase < a.repeat; a.phase++) {  // action_repeat: the same action, k launches
       if (e->cull) {
         if (fused) {
@@ -4148,13 +4180,17 @@ static int launch_steps(pp3_env_t* e, const float* actions_dev, int64_t action_s
       }
       HIPCHK(hipGetLastError());
     }
+    if (trunc_row && !fused) {  // after the wrapper step's last repeat
+      hipLaunchKernelGGL(trunc_row_kernel, dim3((e->N + 255) / 256), dim3(256), 0, st, a.episode, trunc_row, e->N);
+      HIPCHK(hipGetLastError());
+    }
   }
   return PP3_OK;
 }
 
 int pp3_step(pp3_env_t* e, const float* actions_dev, void* stream) {
   if (!e || !actions_dev) return set_err(PP3_ERR_ARG, "pp3_step: null argument");
-  return launch_steps(e, actions_dev, 0, 1, nullptr, nullptr, nullptr, false, stream);
+  return launch_steps(e, actions_dev, 0, 1, nullptr, nullptr, nullptr, nullptr, false, stream);
 }
 
 int pp3_rollout(pp3_env_t* e, const float* actions_dev, int64_t action_stride, int32_t nsteps, float* reward_dev,
@@ -4162,7 +4198,8 @@ int pp3_rollout(pp3_env_t* e, const float* actions_dev, int64_t action_stride, i
   if (!e || !actions_dev) return set_err(PP3_ERR_ARG, "pp3_rollout: null argument");
   if (nsteps < 1) return set_err(PP3_ERR_ARG, "pp3_rollout: nsteps must be >= 1");
   if (action_stride < 0) return set_err(PP3_ERR_ARG, "pp3_rollout: negative action_stride");
-  return launch_steps(e, actions_dev, action_stride, nsteps, reward_dev, done_dev, obs_dev, true, stream);
+  if (trunc_over(e, nsteps)) return set_err(PP3_ERR_ARG, "pp3_rollout: " + trunc_over_msg(e, nsteps));
+  return launch_steps(e, actions_dev, action_stride, nsteps, reward_dev, done_dev, obs_dev, e->traj_trunc, true, stream);
 }
 
 // Which path pp3_rollout_policy takes on this env: ONE fused launch (env_step_kernel<8, true, 8>)
@@ -4198,6 +4235,7 @@ int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float
   if (pp3_policy_device(policy) != e->device) return set_err(PP3_ERR_ARG, "pp3_rollout_policy: policy and env on different devices");
   if (pp3_policy_net(policy)->in_dim != PP3_OBS_DIM * e->H)
     return set_err(PP3_ERR_ARG, "pp3_rollout_policy: the policy's input width must equal the observation size 36 * observation_history");
+  if (trunc_over(e, nsteps)) return set_err(PP3_ERR_ARG, "pp3_rollout_policy: " + trunc_over_msg(e, nsteps));
   const size_t on = (size_t)e->N * PP3_OBS_DIM * e->H;
   const hipStream_t st = stream_of(e, stream);
 #ifndef PP3_PHASE_PROF
@@ -4230,6 +4268,7 @@ int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float
     a.traj_reward = reward_dev;
     a.traj_done = done_dev;
     a.traj_obs = obs_dev;
+    a.traj_trunc = e->traj_trunc;
     pa.act = actions_dev;
     pa.net = *pp3_policy_net(policy);
     const dim3 grid((e->N + pp3pol::TILE - 1) / pp3pol::TILE), block(WAVE * pp3pol::NWAVE);
@@ -4248,7 +4287,7 @@ int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float
       return set_err(PP3_ERR_ARG, std::string("pp3_rollout_policy: ") + pp3_policy_last_error());
     const int rc = launch_steps(e, act, 0, 1, reward_dev ? reward_dev + (size_t)t * e->N : nullptr,
                                 done_dev ? done_dev + (size_t)t * e->N : nullptr, obs_dev ? obs_dev + (size_t)t * on : nullptr,
-                                false, (void*)st);
+                                e->traj_trunc ? e->traj_trunc + (size_t)t * e->N : nullptr, false, (void*)st);
     if (rc) return rc;
   }
   return PP3_OK;
@@ -4309,6 +4348,7 @@ int pp3_rollout_policy_sample(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps
     return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: policy and env on different devices");
   if (pp3_policy_net(policy)->in_dim != PP3_OBS_DIM * e->H)
     return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: the policy's input width must equal the observation size 36 * observation_history");
+  if (trunc_over(e, nsteps)) return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: " + trunc_over_msg(e, nsteps));
   const size_t on = (size_t)e->N * PP3_OBS_DIM * e->H;
   const hipStream_t st = stream_of(e, stream);
   const int part = e->partitionable;
@@ -4342,6 +4382,7 @@ int pp3_rollout_policy_sample(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps
     a.traj_reward = reward_dev;
     a.traj_done = done_dev;
     a.traj_obs = obs_dev;
+    a.traj_trunc = e->traj_trunc;
     sa.p.act = actions_dev;
     sa.p.net = *pp3_policy_net(policy);
     sa.raw = raw_dev;
@@ -4374,7 +4415,7 @@ int pp3_rollout_policy_sample(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps
       return set_err(PP3_ERR_ARG, std::string("pp3_rollout_policy_sample: ") + pp3_policy_last_error());
     const int rc = launch_steps(e, act, 0, 1, reward_dev ? reward_dev + (size_t)t * e->N : nullptr,
                                 done_dev ? done_dev + (size_t)t * e->N : nullptr, obs_dev ? obs_dev + (size_t)t * on : nullptr,
-                                false, (void*)st);
+                                e->traj_trunc ? e->traj_trunc + (size_t)t * e->N : nullptr, false, (void*)st);
     if (rc) return rc;
   }
   key_out[0] = kt.a;
@@ -4424,6 +4465,14 @@ int pp3_set_auto_reset(pp3_env_t* e, int32_t episode_length) {
   }
   e->episode_length = episode_length > 0 ? episode_length : 0;
   if (e->episode_length == 0) e->action_repeat = 1;
+  return PP3_OK;
+}
+
+int pp3_set_truncation_trajectory(pp3_env_t* e, float* trunc_dev, int32_t max_steps) {
+  if (!e) return set_err(PP3_ERR_ARG, "null env");
+  if (trunc_dev && max_steps < 1) return set_err(PP3_ERR_ARG, "pp3_set_truncation_trajectory: max_steps must be >= 1");
+  e->traj_trunc = trunc_dev;
+  e->trunc_steps = trunc_dev ? max_steps : 0;
   return PP3_OK;
 }
 

@@ -94,6 +94,13 @@ def load() -> C.CDLL:
         for name in ("pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample",
                      "pp3_rollout_policy_sample_timed"):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, "pp3_gae"):  # (the PPO batch; absent from earlier builds run in kernel A/B)
+        f32 = C.c_float
+        L.pp3_set_truncation_trajectory.argtypes = [vp, vp, i32]
+        L.pp3_gae.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp]
+        L.pp3_set_truncation_trajectory.restype = C.c_int
+        L.pp3_gae.restype = C.c_int
+        L.pp3_ppo_last_error.restype = C.c_char_p
     L.pp3_stream.argtypes = [vp]
     L.pp3_stream.restype = vp
     if hasattr(L, "pp3_event_create"):  # (absent from pre-round-5 builds run in kernel A/B: no host-API step there)
@@ -161,6 +168,7 @@ EXPORTED_SYMBOLS = (
     "pp3_policy_create", "pp3_policy_act", "pp3_policy_out_dim", "pp3_policy_destroy", "pp3_policy_last_error",
     "pp3_rollout_policy", "pp3_rollout_policy_timed",
     "pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample", "pp3_rollout_policy_sample_timed",
+    "pp3_set_truncation_trajectory", "pp3_gae", "pp3_ppo_last_error",
     "pp3_stream", "pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy",
     "pp3_set_terrain", "pp3_terrain_slots",
     "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_comm_rank", "pp3_comm_world",

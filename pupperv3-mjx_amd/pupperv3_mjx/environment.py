@@ -569,6 +569,10 @@ class PupperV3Env:
         for b in getattr(self, "_samp_bufs", None) or ():
             b.free()
         self._samp_bufs = None
+        for b in [getattr(self, "_trunc_buf", None)] + list(getattr(self, "_ppo_bufs", None) or ()):
+            if b is not None:
+                b.free()
+        self._trunc_buf = self._ppo_bufs = self._ppo_dev = None
         # free page-locked blocks go with their pools; leased ones are freed when their arrays die
         if getattr(self, "_pin_pool", None) is not None:
             self._pin_pool.retire()
@@ -798,12 +802,14 @@ class PupperV3Env:
             raise
         qb.slot.record()
 
-    def rollout(self, state: State, actions) -> Tuple[State, Dict[str, np.ndarray]]:
+    def rollout(self, state: State, actions, truncation: bool = False) -> Tuple[State, Dict[str, np.ndarray]]:
         """The unroll of brax's generate_unroll ([ext] brax 0.12.1 training/acting.py: a lax.scan of
         env.step) with the K actions given up front, as ONE fused launch: returns the state after
         the last step (what K step() calls return) and the per-step trajectory {"obs": [K, N, 36H],
         "reward": [K, N], "done": [K, N]} (single-env states: [K, 36H] / [K]).  Bit for bit the
-        same as K step() calls."""
+        same as K step() calls.  `truncation=True` adds "truncation" [K, N]: EpisodeWrapper's
+        info["truncation"] after each step (all zeros without auto-reset), which `done` alone does
+        not determine (pp3_set_truncation_trajectory)."""
         self._flush()
         single = _single_of(state)
         n, D = self.num_envs, self.observation_size
@@ -816,16 +822,23 @@ class PupperV3Env:
         blk = self._traj_block(K)
         bufs = self._rollout_buffers(K, outputs=blk is None)
         bufs[0].upload(act)
+        tb = self._trunc_begin(K) if truncation else None
         if blk is not None:
             # the trajectory lands in one page-locked block that the fused launch stores into through
             # its device mapping (no copy after the launch; the arrays are views that keep it leased)
             lease, (p_obs, p_rew, p_done) = blk
-            self.rollout_device(bufs[0].ptr.value, n * _abi.NU, K, p_rew, p_done, p_obs)
+            try:
+                self.rollout_device(bufs[0].ptr.value, n * _abi.NU, K, p_rew, p_done, p_obs)
+            finally:
+                self._trunc_end(tb)
             self.synchronize()
             obs, rew, done = self._traj_views(lease, K)
         else:  # a long unroll: device buffers, copied out after the launch
-            self.rollout_device(bufs[0].ptr.value, n * _abi.NU, K, bufs[1].ptr.value, bufs[2].ptr.value,
-                                bufs[3].ptr.value)
+            try:
+                self.rollout_device(bufs[0].ptr.value, n * _abi.NU, K, bufs[1].ptr.value, bufs[2].ptr.value,
+                                    bufs[3].ptr.value)
+            finally:
+                self._trunc_end(tb)
             self.synchronize()
             rew = np.empty((K, n), np.float32)
             done = np.empty((K, n), np.float32)
@@ -833,16 +846,20 @@ class PupperV3Env:
             for b, a in zip(bufs[1:], (rew, done, obs)):
                 b.download(a)
         traj = {"obs": obs, "reward": rew, "done": done}
+        if tb is not None:
+            traj["truncation"] = self._trunc_rows(tb, K)
         if single:
             traj = {k: v[:, 0] for k, v in traj.items()}
         return self._issue(single), traj
 
-    def rollout_policy(self, state: State, policy, nsteps: int) -> Tuple[State, Dict[str, np.ndarray]]:
+    def rollout_policy(self, state: State, policy, nsteps: int,
+                       truncation: bool = False) -> Tuple[State, Dict[str, np.ndarray]]:
         """brax's generate_unroll with the policy in the loop, on device (pp3_rollout_policy):
         `policy` (an `export.DevicePolicy` with 12 outputs) acts on the env's observation buffer
         before each of the `nsteps` steps; no host round trip until the end.  Returns the state
         after the last step and {"obs": [K, N, 36H], "action": [K, N, 12], "reward": [K, N],
-        "done": [K, N]} (single-env states: without the N axis)."""
+        "done": [K, N]} (single-env states: without the N axis), and with `truncation=True`
+        "truncation" [K, N] as in rollout()."""
         self._flush()
         single = _single_of(state)
         n, D, K = self.num_envs, self.observation_size, int(nsteps)
@@ -854,8 +871,12 @@ class PupperV3Env:
         bufs = self._rollout_buffers(K, outputs=blk is None)
         self._before_launch()
         outs = blk[1] if blk is not None else (bufs[3].ptr.value, bufs[1].ptr.value, bufs[2].ptr.value)
-        _lib.check(self._L.pp3_rollout_policy(self._h, policy._h, K, bufs[0].ptr, C.c_void_p(outs[1]),
-                                              C.c_void_p(outs[2]), C.c_void_p(outs[0]), None))
+        tb = self._trunc_begin(K) if truncation else None
+        try:
+            _lib.check(self._L.pp3_rollout_policy(self._h, policy._h, K, bufs[0].ptr, C.c_void_p(outs[1]),
+                                                  C.c_void_p(outs[2]), C.c_void_p(outs[0]), None))
+        finally:
+            self._trunc_end(tb)
         self.synchronize()
         traj = {"action": np.empty((K, n, _abi.NU), np.float32)}  # (the actions stay on the device for the steps)
         bufs[0].download(traj["action"])
@@ -866,11 +887,14 @@ class PupperV3Env:
                         done=np.empty((K, n), np.float32))
             for b, k in zip(bufs[1:], ("reward", "done", "obs")):
                 b.download(traj[k])
+        if tb is not None:
+            traj["truncation"] = self._trunc_rows(tb, K)
         if single:
             traj = {k: v[:, 0] for k, v in traj.items()}
         return self._issue(single), traj
 
-    def rollout_policy_sample(self, state: State, policy, nsteps: int, key) -> Tuple[State, Dict[str, np.ndarray], np.ndarray]:
+    def rollout_policy_sample(self, state: State, policy, nsteps: int, key,
+                              truncation: bool = False) -> Tuple[State, Dict[str, np.ndarray], np.ndarray]:
         """Brax PPO's data collection (generate_unroll with the training actor in the loop), on
         device (pp3_rollout_policy_sample): `policy` is an `export.DevicePolicy` made from
         `export.convert_training_params`; before each of the `nsteps` steps it draws
@@ -888,7 +912,9 @@ class PupperV3Env:
         reward = traj["reward"][t]; discount = 1 - traj["done"][t]; next_observation =
         traj["obs"][t]; extras.policy_extras = {"raw_action": traj["raw_action"][t], "log_prob":
         traj["log_prob"][t]}.  With auto-reset, traj["obs"][t] of a done step is already the next
-        episode's first observation, as in Brax.  Per-step truncation is not in the trajectory."""
+        episode's first observation, as in Brax.  `truncation=True` adds "truncation" [K, N]
+        (extras.state_extras["truncation"], as in rollout()); collect_ppo returns the whole batch
+        with values and GAE targets."""
         self._flush()
         single = _single_of(state)
         n, D, K = self.num_envs, self.observation_size, int(nsteps)
@@ -903,9 +929,13 @@ class PupperV3Env:
         sbuf = self._sample_buffers(K)
         self._before_launch()
         outs = blk[1] if blk is not None else (bufs[3].ptr.value, bufs[1].ptr.value, bufs[2].ptr.value)
-        _lib.check(self._L.pp3_rollout_policy_sample(
-            self._h, policy._h, K, k_in.ctypes.data_as(C.c_void_p), k_out.ctypes.data_as(C.c_void_p), bufs[0].ptr,
-            sbuf[0].ptr, sbuf[1].ptr, C.c_void_p(outs[1]), C.c_void_p(outs[2]), C.c_void_p(outs[0]), None))
+        tb = self._trunc_begin(K) if truncation else None
+        try:
+            _lib.check(self._L.pp3_rollout_policy_sample(
+                self._h, policy._h, K, k_in.ctypes.data_as(C.c_void_p), k_out.ctypes.data_as(C.c_void_p), bufs[0].ptr,
+                sbuf[0].ptr, sbuf[1].ptr, C.c_void_p(outs[1]), C.c_void_p(outs[2]), C.c_void_p(outs[0]), None))
+        finally:
+            self._trunc_end(tb)
         self.synchronize()
         traj = {"action": np.empty((K, n, _abi.NU), np.float32), "raw_action": np.empty((K, n, _abi.NU), np.float32),
                 "log_prob": np.empty((K, n), np.float32)}
@@ -919,9 +949,122 @@ class PupperV3Env:
                         done=np.empty((K, n), np.float32))
             for b, k in zip(bufs[1:], ("reward", "done", "obs")):
                 b.download(traj[k])
+        if tb is not None:
+            traj["truncation"] = self._trunc_rows(tb, K)
         if single:
             traj = {k: v[:, 0] for k, v in traj.items()}
         return self._issue(single), traj, k_out
+
+    def collect_ppo(self, state: State, policy, value, nsteps: int, key, discount: float = 0.97,
+                    gae_lambda: float = 0.95,
+                    reward_scaling: float = 1.0) -> Tuple[State, Dict[str, np.ndarray], np.ndarray]:
+        """One PPO batch without the trajectory leaving the device between the env step and the
+        targets: rollout_policy_sample's unroll (same returned state and key chain), the critic
+        `value` (an `export.DevicePolicy` of `export.convert_value_params`, one output) on the K + 1
+        observations, and Brax's compute_gae ([ext] brax 0.12.1 training/agents/ppo/losses.py;
+        pp3_gae, whose recurrence include/pupper_hip.h states) on reward * reward_scaling, done,
+        truncation and those values.  All on the env's stream, no host round trip between them.
+
+        Returns (state, batch, K_nsteps).  batch = rollout_policy_sample's keys ("obs" stays the
+        next observation of each step) plus "observation" [K, N, 36H] (what the actor saw at each
+        step: row 0 is the observation the unroll started from), "truncation" [K, N], "value"
+        [K, N], "bootstrap_value" [N] (the critic on the last next observation), "value_target"
+        [K, N] (compute_gae's vs) and "advantage" [K, N]; single-env states: without the N axis.
+        The same arrays stay on the device: ppo_device_batch()."""
+        self._flush()
+        single = _single_of(state)
+        n, D, K = self.num_envs, self.observation_size, int(nsteps)
+        if K < 1:
+            raise ValueError("nsteps must be >= 1")
+        if value.out_dim != 1 or value.in_dim != D:
+            raise ValueError(f"the value network must map {D} inputs to 1 output "
+                             f"(got {value.in_dim} -> {value.out_dim}; export.convert_value_params)")
+        if not all(np.isfinite(x) for x in (discount, gae_lambda, reward_scaling)):
+            raise ValueError("discount, gae_lambda and reward_scaling must be finite")
+        k_in = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+        k_out = np.zeros(2, dtype=np.uint32)
+        if not self.holds(state):
+            self._write_state(state)
+        act_buf = self._rollout_buffers(K, outputs=False)[0]
+        sbuf = self._sample_buffers(K)
+        obs_all, val_all, rew, done, vs, adv = (b.ptr.value for b in self._ppo_buffers(K))
+        self._before_launch()
+        stream = self._L.pp3_stream(self._h)
+        obs_ptr, _ = self.device_field(_abi.F_OBS)
+        _lib.check(self._L.pp3_memcpy_d2d(C.c_void_p(obs_all), C.c_void_p(obs_ptr), 4 * n * D, C.c_void_p(stream)))
+        tb = self._trunc_begin(K)
+        try:
+            _lib.check(self._L.pp3_rollout_policy_sample(
+                self._h, policy._h, K, k_in.ctypes.data_as(C.c_void_p), k_out.ctypes.data_as(C.c_void_p), act_buf.ptr,
+                sbuf[0].ptr, sbuf[1].ptr, C.c_void_p(rew), C.c_void_p(done), C.c_void_p(obs_all + 4 * n * D), None))
+        finally:
+            self._trunc_end(tb)
+        value.act(obs_all, D, (K + 1) * n, val_all, 1, stream)  # row K: the bootstrap value
+        rc = self._L.pp3_gae(self.device, K, n, n, C.c_void_p(rew), C.c_void_p(done), tb.ptr, C.c_void_p(val_all),
+                             C.c_void_p(val_all + 4 * K * n), float(discount), float(gae_lambda), float(reward_scaling),
+                             C.c_void_p(vs), C.c_void_p(adv), C.c_void_p(stream))
+        if rc != 0:
+            raise _lib.PupperHipError(f"pupper_hip error {rc}: {self._L.pp3_ppo_last_error().decode(errors='replace')}")
+        self._ppo_dev = {
+            "observation": (obs_all, (K, n, D)), "obs": (obs_all + 4 * n * D, (K, n, D)),
+            "action": (act_buf.ptr.value, (K, n, _abi.NU)), "raw_action": (sbuf[0].ptr.value, (K, n, _abi.NU)),
+            "log_prob": (sbuf[1].ptr.value, (K, n)), "reward": (rew, (K, n)), "done": (done, (K, n)),
+            "truncation": (tb.ptr.value, (K, n)), "value": (val_all, (K, n)),
+            "bootstrap_value": (val_all + 4 * K * n, (n,)), "value_target": (vs, (K, n)), "advantage": (adv, (K, n))}
+        self.synchronize()
+        host = {"obs_all": np.empty((K + 1, n, D), np.float32), "val_all": np.empty((K + 1, n), np.float32)}
+        for name, ptr in (("obs_all", obs_all), ("val_all", val_all)):
+            _lib.check(self._L.pp3_memcpy_d2h(host[name].ctypes.data_as(C.c_void_p), C.c_void_p(ptr), host[name].nbytes))
+        batch = {"observation": host["obs_all"][:K], "obs": host["obs_all"][1:], "value": host["val_all"][:K]}
+        for name in ("action", "raw_action", "log_prob", "reward", "done", "truncation", "value_target", "advantage"):
+            ptr, shape = self._ppo_dev[name]
+            batch[name] = np.empty(shape, np.float32)
+            _lib.check(self._L.pp3_memcpy_d2h(batch[name].ctypes.data_as(C.c_void_p), C.c_void_p(ptr), batch[name].nbytes))
+        if single:
+            batch = {k: v[:, 0] for k, v in batch.items()}
+        batch["bootstrap_value"] = host["val_all"][K, 0] if single else host["val_all"][K]
+        return self._issue(single), batch, k_out
+
+    def ppo_device_batch(self) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
+        """{name: (device address, shape)} of the last collect_ppo batch (f32, C order, the batched
+        shapes), for a learner on the same GPU; valid until the next collect_ppo or rollout* call."""
+        if getattr(self, "_ppo_dev", None) is None:
+            raise ValueError("ppo_device_batch: no collect_ppo batch on the device yet")
+        return dict(self._ppo_dev)
+
+    def _ppo_buffers(self, K: int) -> list:
+        """Device buffers of collect_ppo(): obs_all [K+1][N][36H], values_all [K+1][N], reward, done,
+        value targets and advantages [K][N]; kept and grown."""
+        cur = getattr(self, "_ppo_bufs", None)
+        n, D = self.num_envs, self.observation_size
+        sizes = [4 * (K + 1) * n * D, 4 * (K + 1) * n] + [4 * K * n] * 4
+        if cur is None or any(b.nbytes < s for b, s in zip(cur, sizes)):
+            if cur is not None:
+                for b in cur:
+                    b.free()
+            cur = [_lib.DeviceBuffer(sz, self.device) for sz in sizes]
+            self._ppo_bufs = cur
+        return cur
+
+    def _trunc_begin(self, K: int):
+        """Registers the truncation row buffer (kept and grown) for one K-step rollout launch."""
+        cur = getattr(self, "_trunc_buf", None)
+        if cur is None or cur.nbytes < 4 * K * self.num_envs:
+            if cur is not None:
+                cur.free()
+            cur = self._trunc_buf = _lib.DeviceBuffer(4 * K * self.num_envs, self.device)
+        _lib.check(self._L.pp3_set_truncation_trajectory(self._h, cur.ptr, K))
+        return cur
+
+    def _trunc_end(self, tb) -> None:
+        """Unregisters it: step() and every other rollout write no truncation rows."""
+        if tb is not None and self._h:
+            _lib.check(self._L.pp3_set_truncation_trajectory(self._h, None, 0))
+
+    def _trunc_rows(self, tb, K: int) -> np.ndarray:
+        out = np.empty((K, self.num_envs), np.float32)
+        tb.download(out)
+        return out
 
     def _sample_buffers(self, K: int) -> list:
         """Device buffers of rollout_policy_sample(): raw actions and log-probs for K steps; kept and grown."""

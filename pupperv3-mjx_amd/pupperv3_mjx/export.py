@@ -137,6 +137,20 @@ def convert_training_params(params, activation: str, action_scale: float, kp: fl
     return out
 
 
+def convert_value_params(params, activation: str, observation_history: int) -> Dict[str, Any]:
+    """Brax PPO's value network ([ext] brax 0.12.1 training/agents/ppo/networks.py make_value_network:
+    an MLP on the normalised observation whose last layer has one column; from memory) in the
+    dict form of `convert_params`: params = (normalizer with .mean/.std, {"params": {layer:
+    {"kernel", "bias"}}}), normalisation folded into layer 0, hidden layers `activation`, the last
+    layer "linear" with shape [None, 1].  It has no actuator keys and no distribution:
+    `policy_forward` is its meaning and `DevicePolicy.act` with action_stride 1 runs it (the critic
+    of `PupperV3Env.collect_ppo`)."""
+    layers, input_size = _dense_layers(params, activation, final_activation="linear", split_head=False)
+    if layers[-1]["shape"][1] != 1:
+        raise ValueError(f"a value network's last layer has one column, this one has {layers[-1]['shape'][1]}")
+    return {"observation_history": observation_history, "in_shape": [None, input_size], "layers": layers}
+
+
 def _softplus(x):
     return np.maximum(x, 0) + np.log1p(np.exp(-np.abs(x)))
 

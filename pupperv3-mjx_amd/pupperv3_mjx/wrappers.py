@@ -96,23 +96,34 @@ class AutoResetEpisodeEnv:
         self._prepare(state)
         return self.env.step(state, action)
 
-    def rollout(self, state: State, actions):
+    def rollout(self, state: State, actions, truncation: bool = False):
         """K wrapper steps as one fused launch (PupperV3Env.rollout; action_repeat > 1 keeps its
         k launches per step): (state after the last step, {"obs", "reward", "done"} per step)."""
         self._prepare(state)
-        return self.env.rollout(state, actions)
+        return self.env.rollout(state, actions, truncation=truncation)
 
-    def rollout_policy(self, state: State, policy, nsteps: int):
+    def rollout_policy(self, state: State, policy, nsteps: int, truncation: bool = False):
         """K wrapper steps with the on-device policy in the loop (PupperV3Env.rollout_policy)."""
         self._prepare(state)
-        return self.env.rollout_policy(state, policy, nsteps)
+        return self.env.rollout_policy(state, policy, nsteps, truncation=truncation)
 
-    def rollout_policy_sample(self, state: State, policy, nsteps: int, key):
+    def rollout_policy_sample(self, state: State, policy, nsteps: int, key, truncation: bool = False):
         """K wrapper steps of PPO data collection, the sampling actor in the loop
         (PupperV3Env.rollout_policy_sample: (state, traj, next_key); its docstring says how a
         transition is assembled)."""
         self._prepare(state)
-        return self.env.rollout_policy_sample(state, policy, nsteps, key)
+        return self.env.rollout_policy_sample(state, policy, nsteps, key, truncation=truncation)
+
+    def collect_ppo(self, state: State, policy, value, nsteps: int, key, discount: float = 0.97,
+                    gae_lambda: float = 0.95, reward_scaling: float = 1.0):
+        """One PPO batch of K wrapper steps with values and GAE targets (PupperV3Env.collect_ppo:
+        (state, batch, next_key))."""
+        self._prepare(state)
+        return self.env.collect_ppo(state, policy, value, nsteps, key, discount, gae_lambda, reward_scaling)
+
+    def ppo_device_batch(self):
+        """PupperV3Env.ppo_device_batch: the last collect_ppo batch's device addresses."""
+        return self.env.ppo_device_batch()
 
     def _prepare(self, state: State) -> None:
         n = self.env.num_envs
