@@ -1423,12 +1423,15 @@ __device__ __forceinline__ void row_dotk(const Shared<NC>& s, int r, int nl, int
           "+v"(jj[8]), "+v"(xv[0][0]), "+v"(xv[0][1]), "+v"(xv[0][2]), "+v"(xv[0][3]), "+v"(xv[0][4]),
           "+v"(xv[0][5]), "+v"(xv[0][6]), "+v"(xv[0][7]), "+v"(xv[0][8]), "+v"(x1[0]));
     } else {
-      static_assert(K == 2, "row_dotk: K = 1 or 2");
+      static_assert(K == 2 || K == 3, "row_dotk: K = 1, 2 or 3");
       PIN("+v"(jj[0]), "+v"(jj[1]), "+v"(jj[2]), "+v"(jj[3]), "+v"(jj[4]), "+v"(jj[5]), "+v"(jj[6]), "+v"(jj[7]),
           "+v"(jj[8]), "+v"(xv[0][0]), "+v"(xv[0][1]), "+v"(xv[0][2]), "+v"(xv[0][3]), "+v"(xv[0][4]),
           "+v"(xv[0][5]), "+v"(xv[0][6]), "+v"(xv[0][7]), "+v"(xv[0][8]), "+v"(xv[1][0]), "+v"(xv[1][1]),
           "+v"(xv[1][2]), "+v"(xv[1][3]), "+v"(xv[1][4]), "+v"(xv[1][5]), "+v"(xv[1][6]), "+v"(xv[1][7]),
           "+v"(xv[1][8]), "+v"(x1[0]), "+v"(x1[1]));
+      if constexpr (K == 3)  // (an asm statement takes 30 operands: the third vector's in a second one)
+        PIN("+v"(xv[2][0]), "+v"(xv[2][1]), "+v"(xv[2][2]), "+v"(xv[2][3]), "+v"(xv[2][4]), "+v"(xv[2][5]),
+            "+v"(xv[2][6]), "+v"(xv[2][7]), "+v"(xv[2][8]), "+v"(x1[2]));
     }
 #pragma unroll
     for (int i = 0; i < 9; i++)
@@ -1448,16 +1451,6 @@ __device__ __forceinline__ float row_dot(const Shared<NC>& s, int r, int nl, int
   float o[1];
   row_dotk<NC, 1>(s, r, nl, ncon, xs, o);
   return o[0];
-}
-// J row r dotted with two LDS vectors in one pass
-template <int NC>
-__device__ __forceinline__ void row_dot2(const Shared<NC>& s, int r, int nl, int ncon, const float* x, const float* y,
-                                         float& rx, float& ry) {
-  const float* const xs[2] = {x, y};
-  float o[2];
-  row_dotk<NC, 2>(s, r, nl, ncon, xs, o);
-  rx = o[0];
-  ry = o[1];
 }
 
 // a[j] += w . J[.][j] over the columns [J0, J1) (base: 0..6, leg g: 6+3g..9+3g, dense: 0..18)
@@ -1617,16 +1610,10 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
   int lsup = 4;  // lane c: support of contact c (4 = none)
   { lsup = collision<NC, NWV, CULL>(s, m, l, h, pair_pf, ccache); SYNC(); }
   PHASE(16); l = opaque_lane(l);
-  // the PairCon of contact c = l / 4 for the first batch of phase 13's edge rows (lane e = 4c + k),
-  // loaded here unpinned: it arrives during the limit/actuation and M-entry phases
+  // the PairCon of the contact whose pyramid row this lane holds in row slot 0 of the Newton phase
+  // (row r = l, contact (l - NFR - nl) / 4): fetched unpinned at the end of the limit phase, where nl
+  // is known from the ballot; it arrives during the M-entry and LDL phases
   v4f pcv[4];
-  {
-    const int c = l >> 2;
-    const int p = c < s.ncon ? s.con_pair[c < NC ? c : 0] : 0;
-    const GV4* src = pair_con_groups(m, p);
-#pragma unroll
-    for (int k = 0; k < 4; k++) pcv[k] = src[k];
-  }
   {
     const LaneRec<7> rl = fetch_rec(m.lane_lim, l);
     // every LDS operand of the phase in one pinned round, indices clamped on the lanes that do
@@ -1653,6 +1640,7 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
     }
     const uint32_t mask = hballot(act, h);
     const int slot = __popc(mask & ((1u << l) - 1u));
+    const int nlb = __popc(mask) < NLMAX ? __popc(mask) : NLMAX;
     if (act && slot < NLMAX) {  // (<= one side per hinge: never more than NLMAX rows)
       const int dof = 6 + j - 1;
       const float sg = (l & 1) ? -1.0f : 1.0f;  // J = -side
@@ -1666,7 +1654,7 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
       s.efc_aref[r] = -rl.f[LL_B] * (sg * lqv) - rl.f[LL_K] * imp * (value - rl.f[LL_MARGIN]);
       (void)dof;
     }
-    if (l == 0) s.nl = __popc(mask) < NLMAX ? __popc(mask) : NLMAX;
+    if (l == 0) s.nl = nlb;
     if (l < NFR) {  // dof frictionloss rows (R, b precomputed: pos = 0)
       const int dof = 6 + l;
       s.efc_R[l] = rl.f[LL_FR_R];
@@ -1688,6 +1676,13 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
       s.qfrc_act[d] = gear * force;
     }
     if (l < 6) s.qfrc_act[l] = 0.0f;
+    {  // (clamped index: the lanes of other rows, and of rows past the last contact, fetch pair 0's record)
+      const int pe = l - NFR - nlb, pcon = pe >> 2;
+      const int p = (pe >= 0 && pcon < s.ncon) ? s.con_pair[(pe >= 0 && pcon < NC) ? pcon : 0] : 0;
+      const GV4* src = pair_con_groups(m, p);
+#pragma unroll
+      for (int k = 0; k < 4; k++) pcv[k] = src[k];
+    }
   }
   SYNC();
   PHASE(2); l = opaque_lane(l);
@@ -1751,7 +1746,8 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
   }
   SYNC();
   PHASE(3); l = opaque_lane(l);
-  // ---- phase 5: qfrc_bias/smooth (subtree sums of body forces), contact edge rows ----
+  // ---- phase 5: qfrc_bias/smooth (subtree sums of body forces); the contact edge rows' R, D and
+  // aref are made in the warm start's row pass of phase 7, in the lane that owns the row there ----
   {
   if (l < NV) {
     // base dofs: the whole tree's cfrc; a leg link: itself + the (<= 2) links below (cacc holds
@@ -1793,29 +1789,6 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
   const int nl = s.nl;
   __builtin_assume(nl >= 0 && nl <= NLMAX);
   const int nefc = NFR + nl + 4 * ncon;
-  for (int e = l; e < 4 * ncon; e += HW) {
-    const int c = e >> 2, p = s.con_pair[c], r = NFR + nl + e;
-    LaneRec<4> pc;
-    if (e < HW) {  // first batch (every row when 4 * ncon <= 32): prefetched after the collision
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-#pragma unroll
-        for (int cc = 0; cc < 4; cc++) pc.f[4 * k + cc] = pcv[k][cc];
-    } else {
-      pc = fetch_rec(*reinterpret_cast<const LaneRec<4>*>(&m.pair_con[p]));
-    }
-    const PairCon& q = *reinterpret_cast<const PairCon*>(&pc);
-    const float mu = s.con_mu[c];
-    const float dist = s.con_dist[c];
-    const float vel = row_dot(s, r, nl, ncon, s.qvel);
-    const float tran = q.tran;
-    const float invw = (tran + mu * mu * tran) * 2.0f * mu * mu / m.impratio;
-    const float imp = getimp(q.solimp, dist, q.margin);
-    const float R = fmaxf(MINVAL, (1.0f - imp) / imp * invw);
-    s.efc_R[r] = R;
-    s.efc_D[r] = 1.0f / R;
-    s.efc_aref[r] = -q.b * vel - q.k * imp * (dist - q.margin);
-  }
   SYNC();
   PHASE(13); l = opaque_lane(l);
   // ---- phase 6: qacc_smooth = M^-1 qfrc_smooth (register LDL) ----
@@ -1835,6 +1808,8 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
 
   // ---- phase 7: Newton solver (mj_solNewton), warm-started ----
   // per-lane rows r = l + HW * t
+  // frictionloss and limit rows take D, R and aref from the limit phase's LDS rows; a pyramid row of
+  // a contact gets them in the warm start's row pass below, from J qvel as that pass's third vector
   float Dr[NR], Rr[NR], ar[NR], fl[NR];
   bool valid[NR], isfr[NR];
 #pragma unroll
@@ -1842,6 +1817,9 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
     const int r = l + HW * t;
     valid[t] = r < nefc;
     isfr[t] = r < NFR;
+    // (a contact row's lane reads words nobody wrote this substep and replaces all three below: the
+    // same loads serve the other lanes, and a select on the row kind here cost two spilled VGPRs in
+    // the policy rollouts, profiles/r10_ab/)
     Dr[t] = valid[t] ? s.efc_D[r] : 0.0f;
     Rr[t] = valid[t] ? s.efc_R[r] : 0.0f;
     ar[t] = valid[t] ? s.efc_aref[r] : 0.0f;
@@ -1860,8 +1838,38 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
       xsm[t] = 0.0f;
       if (!valid[t]) continue;
       const int r = l + HW * t;
-      float d1, d2;
-      row_dot2(s, r, nl, ncon, s.qws, s.qacc_smooth, d1, d2);
+      // a contact row's own operands (indices clamped on the other rows), with the row's metadata
+      const int e0 = r - NFR - nl, cc = e0 < 0 ? 0 : ((e0 >> 2) < NC ? (e0 >> 2) : NC - 1);
+      // contact edge row: R, D and all of aref but the velocity term first, so that the PairCon's
+      // registers are free again in the row pass (row slot 0: prefetched after the limit phase)
+      float cb = 0.0f, cp = 0.0f;
+      if (e0 >= 0) {
+        const float mu = s.con_mu[cc];
+        const float dist = s.con_dist[cc];
+        LaneRec<4> pc;
+        if (t == 0) {
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int c4 = 0; c4 < 4; c4++) pc.f[4 * k + c4] = pcv[k][c4];
+        } else {
+          pc = fetch_rec(*reinterpret_cast<const LaneRec<4>*>(&m.pair_con[s.con_pair[cc]]));
+        }
+        const PairCon& q = *reinterpret_cast<const PairCon*>(&pc);
+        const float tran = q.tran;
+        const float invw = (tran + mu * mu * tran) * 2.0f * mu * mu / m.impratio;
+        const float imp = getimp(q.solimp, dist, q.margin);
+        const float R = fmaxf(MINVAL, (1.0f - imp) / imp * invw);
+        Rr[t] = R;
+        Dr[t] = 1.0f / R;
+        cb = q.b;
+        cp = q.k * imp * (dist - q.margin);
+      }
+      const float* const xs[3] = {s.qws, s.qacc_smooth, s.qvel};
+      float d[3];
+      row_dotk<NC, 3>(s, r, nl, ncon, xs, d);
+      ar[t] = e0 >= 0 ? -cb * d[2] - cp : ar[t];  // (J qvel of the other rows is not used)
+      const float d1 = d[0], d2 = d[1];
       const float x1 = d1 - ar[t];
       const float x2 = d2 - ar[t];
       xws[t] = x1;
