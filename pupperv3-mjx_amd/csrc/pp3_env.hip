@@ -160,6 +160,13 @@ constexpr bool shared_operands_aligned() {
 }
 static_assert(shared_operands_aligned<8>() && shared_operands_aligned<16>(), "Shared: aligned operand arrays");
 static_assert(offsetof(Shared<8>, cfrc_base) % 8 == 4 && offsetof(Shared<8>, nl) % 8 == 4, "Shared: the tail sits at odd word offsets");
+// ldl_arrow_solve's window at the head of s.x.L: four pivot rows of 20 words (18 column entries,
+// the pivot's 1/D, its rhs), the non-pivot lanes' 8-byte dummy behind them; the Schur exchange reuses
+// its first 55 words.  Nothing else in the union is live in the two phases that call it (the M
+// solve follows the last read of s.x.a, the rne forces; the Newton phase owns s.x.L).
+constexpr int LDL_ARROW_WIN = 4 * 20 + 2;
+static_assert(sizeof(Scratch<8>::L) >= LDL_ARROW_WIN * sizeof(float) && sizeof(Scratch<16>::L) >= LDL_ARROW_WIN * sizeof(float) &&
+              (4 * 20) % 2 == 0, "ldl_arrow_solve: the window fits s.x.L, its dummy words are 8-byte aligned");
 
 // A workgroup is ONE wave and LDS executes a wave's instructions in issue order, so a lane's
 // LDS store is visible to every later LDS load of the same wave: phase boundaries only need to
@@ -1078,33 +1085,43 @@ __device__ __forceinline__ float dpp_shl2(float v) { return dpp_f<0x102, 0xF>(v,
 // x_p.  Elimination only updates rows below the pivot, so every lane keeps its row of U (= the
 // row at the time it became pivot) and U x = y is back-substituted from registers:
 //  * 3 leg rounds (4 legs at once): each lane publishes its pivot-column entry, the pivot lane
-//    also its rhs; rows below update their entries and rhs (forward substitution fused in);
+//    also its 1/D and its rhs (one 8-byte store); rows below update their entries and rhs (forward
+//    substitution fused in).  The reciprocal is computed ONCE, by the lane that owns the pivot,
+//    from its own registers, and comes back in the 16-byte word that brings the rhs: the readers
+//    run no v_max / v_rcp per pivot (12 of each per call on every lane before), and nothing pins
+//    the loaded value, so the pivot rows stream behind partial lgkmcnt waits.  The pivot column is
+//    read from the ROW lanes (entry [j][k] of lane j), not from the pivot lane's own row [k][j]:
+//    the two differ in their last bit from round 1 on ((x ik) y against (y ik) x), so a scheme
+//    that eliminates from the pivot lane's row computes other results;
 //  * ONE exchange of the base Schur complement S and its rhs, then every lane factors and solves
 //    the 6x6 base block in registers (x_base on every lane);
 //  * leg rows back-substitute against x_base from registers and against the rows below them in
 //    the same leg through two DPP lane shifts (a leg's rows are adjacent lanes of one DPP row).
 // No transposed factor in LDS and no per-pivot lane broadcasts (cf. mj_factorM / mj_solveM).
-__device__ __forceinline__ float ldl_arrow_solve(float (&a)[NV], float b, int l, float* col /* >= 80 floats */) {
+__device__ __forceinline__ float ldl_arrow_solve(float (&a)[NV], float b, int l, float* col /* >= LDL_ARROW_WIN floats */) {
   l = opaque_lane(l);
-  const int slot = l < NV ? l : NV;
   const int lp = l < NV ? l : NV - 1;
-  // lane p < 12 is the pivot of leg p / 3 in round p % 3; its 1/D is the reciprocal of the value
-  // it publishes then (its own diagonal), read back with that round's pivot columns: one select
-  // per round instead of a compare and select per pivot (12 per call)
+  // the dummy lanes mirror row NV - 1 and store its values to its words: word 18 of each leg's row
+  // is free for the pivot's 1/D
+  const int slot = lp;
+  // lane p < 12 is the pivot of leg p / 3 in round p % 3; its 1/D is the reciprocal of its own
+  // diagonal at that round, kept for the back substitution by one select per round
   const int pg = lp < 12 ? lp / 3 : 0, pst = lp < 12 ? lp - 3 * pg : 3;
-  float mydiag = 1.0f;
+  float dinv = 1.0f;
 #pragma unroll
   for (int st = 0; st < 3; st++) {
 #pragma unroll
     for (int g = 0; g < 4; g++) col[20 * g + slot] = a[3 * g + st];
-    // the four pivots' rhs (lane 3 g + st of leg g) in one store on every lane, the other lanes'
-    // into the dummy lanes' slot (col[18], never used): no EXEC region around one ds_write
-    col[(l < 12 && pst == st) ? 20 * pg + 19 : NV] = b;
+    // a leg lane's entry of its own leg's column st, its diagonal in the round it is pivot: the sum
+    // over the other legs' columns, exact zeros (+0: an entry that starts as +0 stays +0 under the
+    // Hessian's fmas and the rounds' a -= 0 * r); any association of the sum gives the same bits
+    const float own = (a[st] + a[3 + st]) + (a[6 + st] + a[9 + st]);
+    const float oik = frcp(fmaxf(own, MINVAL));
+    dinv = (pst == st) ? oik : dinv;
+    // the four pivots' 1/D and rhs (lane 3 g + st of leg g) in one 8-byte store on every lane, the
+    // other lanes' into col[80..81] (never read): no EXEC region around one ds_write
+    *reinterpret_cast<float2*>(col + ((l < 12 && pst == st) ? 20 * pg + 18 : 80)) = make_float2(oik, b);
     SYNC();
-    {
-      const float pv = col[20 * pg + slot];
-      mydiag = (pst == st) ? pv : mydiag;
-    }
 #pragma unroll
     for (int g = 0; g < 4; g++) {
       const int k = 3 * g + st;
@@ -1126,8 +1143,9 @@ __device__ __forceinline__ float ldl_arrow_solve(float (&a)[NV], float b, int l,
         const float4 v = *reinterpret_cast<const float4*>(c + q);
         r[q] = v.x; r[q + 1] = v.y; r[q + 2] = v.z; r[q + 3] = v.w;
       }
-      float ik = frcp(fmaxf(r[k], MINVAL));
-      PIN("+v"(ik));  // (on every lane: otherwise the pivot read and rcp sink into a branch on l > k)
+      // the pivot lane's frcp(fmaxf(D, MINVAL)): the bits every lane computed from r[k] before.  Not
+      // pinned: a pin here waits for this leg's last word before any leg's FMAs issue
+      const float ik = r[18];
       const float lik = (l > k) ? a[k] * ik : 0.0f;  // zero on rows above the pivot and other legs
 #pragma unroll
       for (int jj = 0; jj < 3; ++jj)
@@ -1186,13 +1204,14 @@ __device__ __forceinline__ float ldl_arrow_solve(float (&a)[NV], float b, int l,
 #pragma unroll
     for (int i = 5; i > c; --i) y[c] = y[c] - S[i][c] * y[i];
   // leg rows: U x = y from registers (base part) and the rows below in the same leg (DPP)
-  const float dinv = frcp(fmaxf(mydiag, MINVAL));  // the pivot's ik (base and dummy lanes: rcp(1) = 1)
+  // (dinv: the pivot's 1/D from its round; base and dummy lanes' x is replaced by y below)
   const int li = pst;  // level in the leg (3 = base row)
   float t = b;
 #pragma unroll
   for (int c = 0; c < 6; c++) t -= a[12 + c] * y[c];
-  // U entries to the next rows of this lane's leg: other legs' columns are exactly zero
-  const float u1 = a[1] + a[4] + a[7] + a[10], u2 = a[2] + a[5] + a[8] + a[11];
+  // U entries to the next rows of this lane's leg: other legs' columns are exactly zero (the sums
+  // of rounds 1 and 2: column 3 g + 1 is final after round 0, column 3 g + 2 after round 1)
+  const float u1 = (a[1] + a[4]) + (a[7] + a[10]), u2 = (a[2] + a[5]) + (a[8] + a[11]);
   float x = t * dinv;                             // level 2 final
   float v1 = dpp_shl1(x);
   x = (li == 1) ? (t - u2 * v1) * dinv : x;       // level 1
