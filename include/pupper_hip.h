@@ -587,6 +587,89 @@ int pp3_gae(int32_t device, int32_t nsteps, int32_t n, int64_t row_stride, const
             float discount, float lambda, float reward_scaling, float* vs, float* adv, void* stream);
 const char* pp3_ppo_last_error(void);
 
+/* ---- PPO learner: loss gradients, Adam, weight reload (additive; PP3_ABI_VERSION stays 2) ----
+ * One PPO iteration on the env's stream with no host round trip: collect, per minibatch loss +
+ * gradient + Adam, reload the actor and the critic, collect again (csrc/pp3_learn.hip).  All f32.
+ * The formulas restate [ext] brax 0.12.1 training/agents/ppo/losses.py compute_ppo_loss and optax
+ * adam from memory; what is written here is the contract.
+ *
+ * Networks: two MLPs in pp3_policy_create's format (at most 8 layers, widths at most
+ * PP3_POLICY_MAX_WIDTH, PP3_ACT_* activations, last layer linear): the policy with 24 outputs and
+ * the PP3_DIST_NORMAL_TANH head (min_std, var_scale), the value net with 1 output.  The trainable
+ * parameters live on the device as one f32 blob per net in pp3_policy_create's `weights` layout
+ * (per layer: kernel [in][out] row-major, then bias [out]), UN-folded: the normaliser is separate.
+ * Gradients and both Adam moments have the same layout.
+ *
+ * Minibatch: the contiguous env range [e0, e0 + B) of a collected batch of N envs and K steps,
+ * R = K B rows, read in place through the row stride N: obs_all [K+1][N][in_dim] (the buffer behind
+ * PupperV3Env.collect_ppo's "observation" and "obs"), raw_action [K][N][12], log_prob / reward /
+ * done / truncation [K][N], the caller's entropy noise eps [K][N][12], and the optional normaliser
+ * mean[in_dim], std[in_dim] (both NULL: identity).
+ *
+ * Loss:
+ *   x = (obs - mean) / std
+ *   baseline[t][e] = V(x[t][e]) for t < K, bootstrap[e] = V(x[K][e])
+ *   (vs, adv) = the pp3_gae recurrence on reward, done, truncation, baseline, bootstrap with
+ *       discount, gae_lambda, reward_scaling; both are constants for the gradient, and the
+ *       bootstrap rows receive none
+ *   normalize_advantage: adv <- (adv - mean_R adv) / (std_R adv + 1e-8), the population std
+ *   logits = pi(x[t][e]) for t < K; loc = logits[0:12], s = logits[12:24],
+ *       scale = (softplus(s) + min_std) * var_scale; logp = the head's log_prob(logits, raw_action)
+ *       as stated above pp3_policy_sample; rho = exp(logp - log_prob)
+ *   policy_loss  = -mean_R min(rho adv, clip(rho, 1 - clip_eps, 1 + clip_eps) adv)
+ *   v_loss       = 0.25 mean_R (vs - baseline)^2
+ *   entropy_loss = -entropy_cost mean_R sum_j [ 1/2 + 1/2 log 2 pi + log scale_j
+ *                                               + 2 (log 2 - a_j - softplus(-2 a_j)) ],
+ *       a_j = loc_j + scale_j eps_j (the gradient flows through a_j into loc and scale)
+ *   total = policy_loss + v_loss + entropy_loss
+ * Outputs: d total / d (every policy and value parameter) into the learner's gradient blobs
+ * (overwritten each call, not accumulated) and metrics_dev f32[4] = total, policy, value, entropy.
+ * The matrix products run on the exact-f32 MFMA; the weight gradient sums rows in chunks of
+ * PP3_LEARN_ROW_CHUNK and the chunks in ascending order, no atomics: a call repeats bit for bit.
+ *
+ * Adam, with c1 = 1 - b1^t and c2 = 1 - b2^t from the host as f32 (no fused multiply-add):
+ *   m <- b1 m + (1 - b1) g;   v <- b2 v + ((1 - b2) g) g;
+ *   p <- p - (lr (m / c1)) / (sqrt(v / c2) + eps)
+ * ------------------------------------------------------------------------------------------- */
+typedef struct pp3_learner pp3_learner_t;
+#define PP3_LEARN_ROW_CHUNK 256
+/* Owns the parameter, gradient and moment blobs of both nets (the moments start at zero, the
+ * parameters from the host blobs given here) and the workspace for minibatches of up to max_rows
+ * rows, counting the bootstrap rows: (K + 1) B <= max_rows.  PP3_ERR_ARG on a null pointer, a
+ * shape outside the format above, a policy not 24 wide, a value net not 1 wide, a non-linear last
+ * layer, min_std < 0, var_scale <= 0, or max_rows outside 2 .. 2^21. */
+int pp3_learner_create(int32_t device, int32_t in_dim, int32_t policy_layers, const int32_t* policy_out_dims,
+                       const int32_t* policy_acts, const float* policy_weights, int32_t value_layers,
+                       const int32_t* value_out_dims, const int32_t* value_acts, const float* value_weights,
+                       float min_std, float var_scale, int64_t max_rows, pp3_learner_t** out);
+int pp3_learner_destroy(pp3_learner_t* learner);
+/* Device pointer and element count of a blob: net 0 = policy, 1 = value; which 0 = parameters,
+ * 1 = gradients, 2 = Adam m, 3 = Adam v. */
+int pp3_learner_buffers(pp3_learner_t* learner, int32_t net, int32_t which, float** ptr, int64_t* count);
+/* The loss and its gradients on one minibatch (all batch pointers on the learner's device).
+ * PP3_ERR_ARG with nothing launched and no output touched: a null pointer (mean and std_dev may
+ * both be NULL, not one of them), batch < 1, nsteps < 1, e0 < 0 or e0 + batch > num_envs,
+ * (nsteps + 1) * batch over max_rows, a non-finite hyper-parameter, clip_eps <= 0. */
+int pp3_ppo_loss_grad(pp3_learner_t* learner, int32_t nsteps, int32_t batch, int32_t num_envs, int32_t e0,
+                      const float* obs_all, const float* raw_action, const float* log_prob, const float* reward,
+                      const float* done, const float* truncation, const float* eps, const float* mean,
+                      const float* std_dev, float discount, float gae_lambda, float reward_scaling, float clip_eps,
+                      float entropy_cost, int32_t normalize_advantage, float* metrics_dev, void* stream);
+/* One Adam step of both nets from their gradient blobs.  PP3_ERR_ARG (nothing launched) on a null
+ * learner, a non-finite argument, c1 <= 0 or c2 <= 0. */
+int pp3_adam_step(pp3_learner_t* learner, float lr, float b1, float b2, float eps, float c1, float c2,
+                  void* stream);
+/* Overwrites an existing handle's fragment-order weights from a device blob in the layout above
+ * (in_dim, n_layers, out_dims: the blob's shape, which must be the handle's; PP3_ERR_ARG before
+ * any launch otherwise, or for a host-side handle).  Layer 0 is folded with the normaliser:
+ *   W'[k][m] = W[k][m] / std[k],   b'[m] = b[m] - sum_k (mean[k] / std[k]) W[k][m], k ascending;
+ * mean_dev and std_dev both NULL: a pure repack, bit for bit what pp3_policy_create packs from the
+ * same values.  The handle then serves pp3_policy_act, pp3_policy_sample and pp3_rollout_policy*
+ * unchanged; work queued on `stream` before this call sees the old weights. */
+int pp3_policy_load_params(pp3_policy_t* policy, const float* params_dev, int32_t in_dim, int32_t n_layers,
+                           const int32_t* out_dims, const float* mean_dev, const float* std_dev, void* stream);
+const char* pp3_learn_last_error(void);
+
 /* ---------------------------------------------------------------------------------------
  * Multi-GPU (no reference code: the reference runs one process per device under
  * Brax PPO's pmap, [ext] brax 0.12.1 brax/training/agents/ppo/train.py, where the env batch is

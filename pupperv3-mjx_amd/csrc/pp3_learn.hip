@@ -1,0 +1,665 @@
+// pp3_learn.hip -- the PPO learner step on the device: compute_ppo_loss's gradients
+// (pp3_ppo_loss_grad), Adam (pp3_adam_step) and the reload of an actor / critic handle from the
+// trained blob (pp3_policy_load_params).  include/pupper_hip.h states the contract.
+//
+// Matrix work: one LDS-tiled GEMM kernel (gemm_kernel) on v_mfma_f32_16x16x4_f32, the exact-f32
+// MFMA of pp3_mlp.h, in three operand shapes per layer:
+//   forward   Y  = act(X W + b)            A = X [R][K],        B = W [K][M]
+//   delta     D' = (D W^T) * act'(Y')      A = D [R][M],        B = W read transposed
+//   gradient  G  = [X 1]^T D               A = X read transposed (+ a row of ones: the bias
+//                                          gradient is row K of G, which is the blob's layout),
+//                                          B = D, summed over rows in chunks of PP3_LEARN_ROW_CHUNK
+//                                          into per-chunk partials, then added in chunk order.
+// A workgroup of 4 waves owns a 64 x 64 output tile (each wave 2 x 2 MFMA tiles), walks the
+// reduction 16 deep per LDS stage, and reads its operands through (row, column) strides with both
+// indices checked: rows past R and columns past a layer's width read as zero and are never
+// dereferenced.  Nothing is accumulated with atomics: every sum has one fixed order, so a call
+// repeats bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include <string>
+#include <vector>
+
+#include "pp3_mlp.h"
+#include "pupper_hip.h"
+
+namespace pp3learn {
+
+using pp3pol::f32x4;
+
+constexpr int BT = 64;       // output tile of a workgroup (rows and columns)
+constexpr int KT = 16;       // reduction depth per LDS stage
+constexpr int LDT = BT + 16; // LDS row stride: the 4 k rows of an MFMA operand land 16 banks apart
+constexpr int NTHREAD = 256;
+constexpr int ROW_CHUNK = PP3_LEARN_ROW_CHUNK;
+constexpr int RED_BLOCK = 1024;  // the single workgroup of the row reductions
+constexpr int NU = PP3_NU;
+
+enum { EPI_FWD = 0, EPI_DELTA = 1, EPI_PARTIAL = 2 };
+
+struct GemmArgs {
+  const float* A;  // A(i, k) = A[i * a_si + k * a_sk]
+  const float* B;  // B(k, n) = B[k * b_sk + n * b_sn]
+  float* C;        // C(i, n) = C[i * c_ld + n] (+ chunk * Mi * c_ld for EPI_PARTIAL)
+  const float* bias;   // EPI_FWD: [Nn]
+  const float* yprev;  // EPI_DELTA: the post-activation output the delta is taken through, [Mi][Nn]
+  int64_t a_si, a_sk, b_sk, b_sn, c_ld;
+  int Mi, Nn, Kd;
+  int kchunk;    // reduction range of blockIdx.z: [z * kchunk, min(Kd, (z + 1) * kchunk))
+  int ones_row;  // >= 0: A(ones_row, k) = 1 for k < Kd (the bias row of the weight gradient)
+  int act;
+};
+
+__device__ __forceinline__ float act_grad_from_output(float y, int act) {
+  switch (act) {
+    case PP3_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
+    case PP3_ACT_ELU: return y > 0.0f ? 1.0f : y + 1.0f;
+    case PP3_ACT_TANH: return 1.0f - y * y;
+    case PP3_ACT_SIGMOID: return y * (1.0f - y);
+    default: return 1.0f;
+  }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(NTHREAD) void gemm_kernel(GemmArgs g) {
+  __shared__ float As[KT][LDT];  // [k][i]
+  __shared__ float Bs[KT][LDT];  // [k][n]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i0 = blockIdx.y * BT, n0 = blockIdx.x * BT;
+  const int kbeg = blockIdx.z * g.kchunk;
+  const int kend = min(g.Kd, kbeg + g.kchunk);
+  const int wi = 32 * (wave >> 1), wj = 32 * (wave & 1);
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; a++)
+#pragma unroll
+    for (int b = 0; b < 2; b++) acc[a][b] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  // each operand is staged along its contiguous index
+  const bool a_kfast = g.a_sk == 1, b_nfast = g.b_sn == 1;
+  for (int k0 = kbeg; k0 < kend; k0 += KT) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      int ii, kk;
+      if (a_kfast) { kk = tid & 15; ii = (tid >> 4) + 16 * j; }
+      else         { ii = tid & 63; kk = (tid >> 6) + 4 * j; }
+      const int i = i0 + ii, k = k0 + kk;
+      float v = 0.0f;
+      if (i < g.Mi && k < kend) v = (i == g.ones_row) ? 1.0f : g.A[(size_t)i * g.a_si + (size_t)k * g.a_sk];
+      As[kk][ii] = v;
+      int nn, kb;
+      if (b_nfast) { nn = tid & 63; kb = (tid >> 6) + 4 * j; }
+      else         { kb = tid & 15; nn = (tid >> 4) + 16 * j; }
+      const int n = n0 + nn, k2 = k0 + kb;
+      Bs[kb][nn] = (n < g.Nn && k2 < kend) ? g.B[(size_t)k2 * g.b_sk + (size_t)n * g.b_sn] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kb = 0; kb < KT / 4; kb++) {
+      const int kr = 4 * kb + (lane >> 4), c = lane & 15;
+      const float a0 = As[kr][wi + c], a1 = As[kr][wi + 16 + c];
+      const float b0 = Bs[kr][wj + c], b1 = Bs[kr][wj + 16 + c];
+      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  float* C = g.C;
+  if (EPI == EPI_PARTIAL) C += (size_t)blockIdx.z * (size_t)g.Mi * (size_t)g.c_ld;
+#pragma unroll
+  for (int ti = 0; ti < 2; ti++)
+#pragma unroll
+    for (int tj = 0; tj < 2; tj++) {
+      const int n = n0 + wj + 16 * tj + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = i0 + wi + 16 * ti + 4 * (lane >> 4) + r;
+        if (i < g.Mi && n < g.Nn) {
+          float v = acc[ti][tj][r];
+          if (EPI == EPI_FWD) v = pp3pol::activate(v + g.bias[n], g.act);
+          if (EPI == EPI_DELTA) v *= act_grad_from_output(g.yprev[(size_t)i * g.Nn + n], g.act);
+          C[(size_t)i * g.c_ld + n] = v;
+        }
+      }
+    }
+}
+
+// a / b to the correctly rounded quotient (but for rare double roundings): the build's fast division is
+// within 2.5 ulp, and one residual step removes that.  For the quotients whose error the loss
+// amplifies: the normalised observation (every logit inherits it) and the head's standardised action
+// (it enters log_prob squared, at |zr| up to ~10).
+__device__ __forceinline__ float div_rn(float a, float b) {
+  const float q = a / b;
+  return fmaf(fmaf(-q, b, a), 1.0f / b, q);
+}
+
+// grad[i] = sum over chunks c ascending of part[c][i]
+__global__ __launch_bounds__(NTHREAD) void sum_partials_kernel(const float* __restrict__ part, int nchunk, int count,
+                                                               float* __restrict__ grad) {
+  const int i = blockIdx.x * NTHREAD + threadIdx.x;
+  if (i >= count) return;
+  float s = 0.0f;
+  for (int c = 0; c < nchunk; c++) s += part[(size_t)c * count + i];
+  grad[i] = s;
+}
+
+// x0[t * B + e][k] = (obs_all[t][e0 + e][k] - mean[k]) / std[k], t <= K
+__global__ __launch_bounds__(NTHREAD) void gather_obs_kernel(const float* __restrict__ obs, const float* __restrict__ mean,
+                                                             const float* __restrict__ stdv, int rows, int B, int N,
+                                                             int e0, int in_dim, float* __restrict__ x0) {
+  const size_t idx = (size_t)blockIdx.x * NTHREAD + threadIdx.x;
+  if (idx >= (size_t)rows * in_dim) return;
+  const int r = (int)(idx / in_dim), k = (int)(idx - (size_t)r * in_dim);
+  const int t = r / B, e = r - t * B;
+  float v = obs[((size_t)t * N + e0 + e) * in_dim + k];
+  if (mean) v = div_rn(v - mean[k], stdv[k]);
+  x0[idx] = v;
+}
+
+// A fixed-order sum by the one workgroup that runs it: thread i adds elements i, i + RED_BLOCK, ..
+// ascending, then the RED_BLOCK sums meet in a binary tree in LDS.  All threads get the result.
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  sh[tid] = v;
+  __syncthreads();
+  for (int s = RED_BLOCK / 2; s > 0; s >>= 1) {
+    if (tid < s) sh[tid] += sh[tid + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+struct RowArgs {
+  const float *reward, *done, *trunc, *old_logp, *raw, *eps;  // the batch, row stride N
+  const float* values;  // [(K + 1) B] the value net's output
+  const float* logits;  // [R][24]
+  float *vs, *adv;      // [R]
+  float *row_a, *row_b; // [R] per-row loss terms
+  float* dvalue;        // [R] d total / d baseline
+  float* dlogits;       // [R][24]
+  float* stats;         // [4]: v_loss, adv mean, adv std
+  float* metrics;       // [4]: total, policy, value, entropy
+  int K, B, N, e0;
+  float discount, lambda, reward_scaling, clip_eps, entropy_cost, min_std, var_scale;
+  int normalize;
+};
+
+// the pp3_gae recurrence on the minibatch's columns (one lane per env), the value loss terms and
+// d v_loss / d baseline
+__global__ __launch_bounds__(NTHREAD) void value_head_kernel(RowArgs a) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * NTHREAD + threadIdx.x;
+  if (e >= a.B) return;
+  const int R = a.K * a.B;
+  float vnext = a.values[(size_t)a.K * a.B + e];
+  float vsnext = vnext, acc = 0.0f;
+  for (int t = a.K - 1; t >= 0; t--) {
+    const size_t at = (size_t)t * a.N + a.e0 + e;
+    const int r = t * a.B + e;
+    const float v = a.values[r];
+    const float tm = 1.0f - a.trunc[at];
+    const float term = a.done[at] * tm;
+    const float g = a.discount * (1.0f - term);
+    const float rw = a.reward[at] * a.reward_scaling;
+    const float delta = ((rw + g * vnext) - v) * tm;
+    acc = delta + (((g * tm) * a.lambda) * acc);
+    const float vs = acc + v;
+    const float ad = ((rw + g * vsnext) - v) * tm;
+    a.vs[r] = vs;
+    a.adv[r] = ad;
+    const float d = vs - v;
+    a.row_a[r] = d * d;
+    a.dvalue[r] = (0.5f * (v - vs)) / (float)R;
+    vnext = v;
+    vsnext = vs;
+  }
+}
+
+// v_loss and the advantage's mean and population std (two passes), one workgroup
+__global__ __launch_bounds__(RED_BLOCK) void value_stats_kernel(RowArgs a) {
+  __shared__ float sh[RED_BLOCK];
+  const int R = a.K * a.B;
+  float s = 0.0f, m = 0.0f;
+  for (int r = threadIdx.x; r < R; r += RED_BLOCK) {
+    s += a.row_a[r];
+    m += a.adv[r];
+  }
+  const float vsum = block_sum(s, sh);
+  const float mean = block_sum(m, sh) / (float)R;
+  float q = 0.0f;
+  for (int r = threadIdx.x; r < R; r += RED_BLOCK) {
+    const float d = a.adv[r] - mean;
+    q += d * d;
+  }
+  const float var = block_sum(q, sh) / (float)R;
+  if (threadIdx.x == 0) {
+    a.stats[0] = 0.25f * (vsum / (float)R);
+    a.stats[1] = mean;
+    a.stats[2] = sqrtf(var);
+  }
+}
+
+__device__ __forceinline__ float softplusf(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// per row: the clipped surrogate and the entropy term, and d total / d logits
+__global__ __launch_bounds__(NTHREAD) void policy_head_kernel(RowArgs a) {
+  const int r = blockIdx.x * NTHREAD + threadIdx.x;
+  const int R = a.K * a.B;
+  if (r >= R) return;
+  const int t = r / a.B, e = r - t * a.B;
+  const size_t at = (size_t)t * a.N + a.e0 + e;
+  const float* lg = a.logits + (size_t)r * 2 * NU;
+  const float* raw = a.raw + at * NU;
+  const float* eps = a.eps + at * NU;
+  float adv = a.adv[r];
+  if (a.normalize) adv = (adv - a.stats[1]) / (a.stats[2] + 1e-8f);
+  const float invR = 1.0f / (float)R;
+  float loc[NU], scale[NU], zr[NU], sg[NU];
+  float logp = 0.0f, ent = 0.0f;
+#pragma unroll
+  for (int j = 0; j < NU; j++) {
+    loc[j] = lg[j];
+    const float s = lg[NU + j];
+    scale[j] = (softplusf(s) + a.min_std) * a.var_scale;
+    sg[j] = sigmoidf(s) * a.var_scale;
+    zr[j] = div_rn(raw[j] - loc[j], scale[j]);
+    const float ls = logf(scale[j]);
+    logp += -0.5f * zr[j] * zr[j] - ls - 0.918938533f - 2.0f * (0.693147181f - raw[j] - softplusf(-2.0f * raw[j]));
+    const float act = loc[j] + scale[j] * eps[j];
+    ent += 0.5f + 0.918938533f + ls + 2.0f * (0.693147181f - act - softplusf(-2.0f * act));
+  }
+  const float rho = expf(logp - a.old_logp[at]);
+  const float rc = fminf(fmaxf(rho, 1.0f - a.clip_eps), 1.0f + a.clip_eps);
+  const float s1 = rho * adv, s2 = rc * adv;
+  a.row_a[r] = fminf(s1, s2);
+  a.row_b[r] = ent;
+  // the minimum is the unclipped branch (or both): its slope in rho is adv; the clipped branch is flat
+  const float dlogp = (s1 <= s2) ? -(adv * rho) * invR : 0.0f;
+  const float dent = -a.entropy_cost * invR;
+  float* dl = a.dlogits + (size_t)r * 2 * NU;
+#pragma unroll
+  for (int j = 0; j < NU; j++) {
+    const float th = tanhf(loc[j] + scale[j] * eps[j]);
+    const float dloc = dlogp * (zr[j] / scale[j]) + dent * (-2.0f * th);
+    const float dscale = dlogp * ((zr[j] * zr[j] - 1.0f) / scale[j]) + dent * (1.0f / scale[j] - 2.0f * th * eps[j]);
+    dl[j] = dloc;
+    dl[NU + j] = dscale * sg[j];
+  }
+}
+
+__global__ __launch_bounds__(RED_BLOCK) void metrics_kernel(RowArgs a) {
+  __shared__ float sh[RED_BLOCK];
+  const int R = a.K * a.B;
+  float p = 0.0f, h = 0.0f;
+  for (int r = threadIdx.x; r < R; r += RED_BLOCK) {
+    p += a.row_a[r];
+    h += a.row_b[r];
+  }
+  const float ps = block_sum(p, sh), hs = block_sum(h, sh);
+  if (threadIdx.x == 0) {
+    const float pl = -(ps / (float)R), el = -a.entropy_cost * (hs / (float)R), vl = a.stats[0];
+    a.metrics[0] = pl + vl + el;
+    a.metrics[1] = pl;
+    a.metrics[2] = vl;
+    a.metrics[3] = el;
+  }
+}
+
+__global__ __launch_bounds__(NTHREAD) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t count,
+                                                       float lr, float b1, float b2, float eps, float c1, float c2) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * NTHREAD + threadIdx.x;
+  if (i >= count) return;
+  const float gi = g[i];
+  const float mi = b1 * m[i] + (1.0f - b1) * gi;
+  const float vi = b2 * v[i] + ((1.0f - b2) * gi) * gi;
+  m[i] = mi;
+  v[i] = vi;
+  p[i] = p[i] - (lr * (mi / c1)) / (sqrtf(vi / c2) + eps);
+}
+
+// One layer of a handle's fragment-order weights from the blob (pp3_policy_create's packing);
+// layer 0 folded with the normaliser when there is one.
+struct RepackArgs {
+  const float* src;  // the layer's kernel [K][M], then bias [M]
+  float* w;          // [ntile][ngrp][64][4]
+  float* b;          // [Mp]
+  const float *mean, *stdv;  // null, or [K]
+  int K, M, Mp, ngrp, ntile;
+};
+__global__ __launch_bounds__(NTHREAD) void repack_kernel(RepackArgs a) {
+#pragma clang fp contract(off)
+  const int idx = blockIdx.x * NTHREAD + threadIdx.x;
+  const int nw = a.ntile * a.ngrp * 256;
+  if (idx < nw) {
+    const int j = idx & 3, ln = (idx >> 2) & 63, tg = idx >> 8;
+    const int g = tg % a.ngrp, t = tg / a.ngrp;
+    const int k = 4 * (4 * g + j) + (ln >> 4), m = pp3pol::TILE * t + (ln & 15);
+    float v = 0.0f;
+    if (k < a.K && m < a.M) {
+      v = a.src[(size_t)k * a.M + m];
+      if (a.stdv) v = div_rn(v, a.stdv[k]);
+    }
+    a.w[idx] = v;
+  } else if (idx < nw + a.Mp) {
+    const int m = idx - nw;
+    float v = 0.0f;
+    if (m < a.M) {
+      v = a.src[(size_t)a.K * a.M + m];
+      if (a.stdv) {
+        float s = 0.0f;
+        for (int k = 0; k < a.K; k++) s += div_rn(a.mean[k], a.stdv[k]) * a.src[(size_t)k * a.M + m];
+        v = v - s;
+      }
+    }
+    a.b[m] = v;
+  }
+}
+
+struct NetShape {
+  int n_layers, in_dim;
+  int K[PP3_POLICY_MAX_LAYERS], M[PP3_POLICY_MAX_LAYERS], act[PP3_POLICY_MAX_LAYERS];
+  size_t off[PP3_POLICY_MAX_LAYERS];  // the layer's kernel in the blob; its bias follows at off + K * M
+  size_t count, width_sum;
+  int max_width;
+};
+
+}  // namespace pp3learn
+
+using namespace pp3learn;
+
+struct pp3_learner {
+  int device;
+  int max_rows;
+  NetShape net[2];  // 0: policy, 1: value
+  float min_std, var_scale;
+  float* blob[2][4];  // params, grads, m, v
+  float* x0;          // [max_rows][in_dim]
+  float* y;           // the layers' outputs of the net in flight, [rows][width] one after another
+  float* d[2];        // deltas, ping-pong, [max_rows][max width]
+  float* part;        // weight-gradient partials [chunks][(K + 1) M]
+  float *vs, *adv, *row_a, *row_b, *stats;
+};
+
+static thread_local std::string g_lerr;
+static int lerr(int code, const std::string& m) {
+  g_lerr = m;
+  return code;
+}
+#define LHIP(x)                                                                                  \
+  do {                                                                                           \
+    hipError_t e_ = (x);                                                                         \
+    if (e_ != hipSuccess) return lerr(PP3_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+static bool net_shape(int in_dim, int n_layers, const int32_t* outs, const int32_t* acts, NetShape& s) {
+  if (!outs || !acts || n_layers < 1 || n_layers > PP3_POLICY_MAX_LAYERS) return false;
+  if (in_dim < 1 || in_dim > PP3_POLICY_MAX_WIDTH) return false;
+  s = NetShape{};
+  s.n_layers = n_layers;
+  s.in_dim = in_dim;
+  int K = in_dim;
+  for (int i = 0; i < n_layers; i++) {
+    if (outs[i] < 1 || outs[i] > PP3_POLICY_MAX_WIDTH) return false;
+    if (acts[i] < PP3_ACT_LINEAR || acts[i] > PP3_ACT_SIGMOID) return false;
+    s.K[i] = K;
+    s.M[i] = outs[i];
+    s.act[i] = acts[i];
+    s.off[i] = s.count;
+    s.count += (size_t)(K + 1) * outs[i];
+    s.width_sum += outs[i];
+    s.max_width = outs[i] > s.max_width ? outs[i] : s.max_width;
+    K = outs[i];
+  }
+  return s.act[n_layers - 1] == PP3_ACT_LINEAR;
+}
+
+static void launch_gemm(int epi, const GemmArgs& g, int nchunk, hipStream_t st) {
+  const dim3 grid((g.Nn + BT - 1) / BT, (g.Mi + BT - 1) / BT, nchunk), block(NTHREAD);
+  if (epi == EPI_FWD) hipLaunchKernelGGL(gemm_kernel<EPI_FWD>, grid, block, 0, st, g);
+  else if (epi == EPI_DELTA) hipLaunchKernelGGL(gemm_kernel<EPI_DELTA>, grid, block, 0, st, g);
+  else hipLaunchKernelGGL(gemm_kernel<EPI_PARTIAL>, grid, block, 0, st, g);
+}
+
+// the outputs of all layers of net `s` on `rows` rows of x0 -> L->y; returns the last layer's
+static const float* forward(pp3_learner* L, const NetShape& s, const float* params, int rows, hipStream_t st) {
+  const float* x = L->x0;
+  float* y = L->y;
+  for (int l = 0; l < s.n_layers; l++) {
+    GemmArgs g{};
+    g.A = x; g.a_si = s.K[l]; g.a_sk = 1;
+    g.B = params + s.off[l]; g.b_sk = s.M[l]; g.b_sn = 1;
+    g.bias = params + s.off[l] + (size_t)s.K[l] * s.M[l];
+    g.C = y; g.c_ld = s.M[l];
+    g.Mi = rows; g.Nn = s.M[l]; g.Kd = s.K[l]; g.kchunk = s.K[l]; g.ones_row = -1; g.act = s.act[l];
+    launch_gemm(EPI_FWD, g, 1, st);
+    x = y;
+    y += (size_t)rows * s.M[l];
+  }
+  return x;
+}
+
+// every layer's gradient from the last layer's delta `dlast` [R][M_last]; the layer outputs in
+// L->y were laid out for `rows` rows per layer (rows >= R)
+static void backward(pp3_learner* L, const NetShape& s, const float* params, float* grads, const float* dlast, int rows,
+                     int R, hipStream_t st) {
+  std::vector<const float*> yl(s.n_layers);
+  const float* y = L->y;
+  for (int l = 0; l < s.n_layers; l++) {
+    yl[l] = y;
+    y += (size_t)rows * s.M[l];
+  }
+  const int nchunk = (R + ROW_CHUNK - 1) / ROW_CHUNK;
+  const float* d = dlast;
+  int pp = 0;
+  for (int l = s.n_layers - 1; l >= 0; l--) {
+    const float* xin = l ? yl[l - 1] : L->x0;
+    GemmArgs g{};  // G = [X 1]^T D
+    g.A = xin; g.a_si = 1; g.a_sk = s.K[l];
+    g.B = d; g.b_sk = s.M[l]; g.b_sn = 1;
+    g.C = L->part; g.c_ld = s.M[l];
+    g.Mi = s.K[l] + 1; g.Nn = s.M[l]; g.Kd = R; g.kchunk = ROW_CHUNK; g.ones_row = s.K[l];
+    launch_gemm(EPI_PARTIAL, g, nchunk, st);
+    const int cnt = (s.K[l] + 1) * s.M[l];
+    hipLaunchKernelGGL(sum_partials_kernel, dim3((cnt + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, st, L->part, nchunk,
+                       cnt, grads + s.off[l]);
+    if (l == 0) break;
+    GemmArgs b{};  // D' = (D W^T) * act'(Y')
+    b.A = d; b.a_si = s.M[l]; b.a_sk = 1;
+    b.B = params + s.off[l]; b.b_sk = 1; b.b_sn = s.M[l];
+    b.C = L->d[pp]; b.c_ld = s.K[l];
+    b.yprev = yl[l - 1];
+    b.Mi = R; b.Nn = s.K[l]; b.Kd = s.M[l]; b.kchunk = s.M[l]; b.ones_row = -1; b.act = s.act[l - 1];
+    launch_gemm(EPI_DELTA, b, 1, st);
+    d = L->d[pp];
+    pp ^= 1;
+  }
+}
+
+extern "C" {
+
+const char* pp3_learn_last_error(void) { return g_lerr.c_str(); }
+
+int pp3_learner_create(int32_t device, int32_t in_dim, int32_t policy_layers, const int32_t* policy_out_dims,
+                       const int32_t* policy_acts, const float* policy_weights, int32_t value_layers,
+                       const int32_t* value_out_dims, const int32_t* value_acts, const float* value_weights,
+                       float min_std, float var_scale, int64_t max_rows, pp3_learner_t** out) {
+  if (!policy_weights || !value_weights || !out) return lerr(PP3_ERR_ARG, "pp3_learner_create: null argument");
+  NetShape ps, vs;
+  if (!net_shape(in_dim, policy_layers, policy_out_dims, policy_acts, ps) || ps.M[policy_layers - 1] != 2 * NU)
+    return lerr(PP3_ERR_ARG, "pp3_learner_create: the policy needs 1..8 layers of width 1..576, a linear last layer of 24");
+  if (!net_shape(in_dim, value_layers, value_out_dims, value_acts, vs) || vs.M[value_layers - 1] != 1)
+    return lerr(PP3_ERR_ARG, "pp3_learner_create: the value net needs 1..8 layers of width 1..576, a linear last layer of 1");
+  if (!(min_std >= 0.0f) || !(min_std < INFINITY) || !(var_scale > 0.0f) || !(var_scale < INFINITY))
+    return lerr(PP3_ERR_ARG, "pp3_learner_create: min_std must be >= 0 and var_scale > 0");
+  if (max_rows < 2 || max_rows > (1 << 21)) return lerr(PP3_ERR_ARG, "pp3_learner_create: max_rows in 2 .. 2^21");
+  if (device < 0) return lerr(PP3_ERR_ARG, "pp3_learner_create: device");
+  LHIP(hipSetDevice(device));
+  pp3_learner* L = new pp3_learner();
+  L->device = device;
+  L->max_rows = (int)max_rows;
+  L->net[0] = ps;
+  L->net[1] = vs;
+  L->min_std = min_std;
+  L->var_scale = var_scale;
+  const size_t rows = (size_t)max_rows;
+  const size_t wsum = ps.width_sum > vs.width_sum ? ps.width_sum : vs.width_sum;
+  size_t wmax = ps.max_width > vs.max_width ? ps.max_width : vs.max_width;
+  if ((size_t)in_dim > wmax) wmax = in_dim;
+  const size_t nchunk = (rows + ROW_CHUNK - 1) / ROW_CHUNK;
+  size_t pmax = 0;
+  for (int n = 0; n < 2; n++)
+    for (int l = 0; l < L->net[n].n_layers; l++) {
+      const size_t c = (size_t)(L->net[n].K[l] + 1) * L->net[n].M[l];
+      pmax = c > pmax ? c : pmax;
+    }
+  bool ok = true;
+  auto alloc = [&](float** p, size_t count) {
+    *p = nullptr;
+    ok = ok && hipMalloc(p, count * sizeof(float)) == hipSuccess && hipMemset(*p, 0, count * sizeof(float)) == hipSuccess;
+  };
+  for (int n = 0; n < 2; n++)
+    for (int w = 0; w < 4; w++) alloc(&L->blob[n][w], L->net[n].count);
+  alloc(&L->x0, rows * in_dim);
+  alloc(&L->y, rows * wsum);
+  alloc(&L->d[0], rows * wmax);
+  alloc(&L->d[1], rows * wmax);
+  alloc(&L->part, nchunk * pmax);
+  alloc(&L->vs, rows);
+  alloc(&L->adv, rows);
+  alloc(&L->row_a, rows);
+  alloc(&L->row_b, rows);
+  alloc(&L->stats, 4);
+  ok = ok && hipMemcpy(L->blob[0][0], policy_weights, ps.count * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && hipMemcpy(L->blob[1][0], value_weights, vs.count * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    pp3_learner_destroy(L);
+    return lerr(PP3_ERR_NOMEM, "pp3_learner_create: device allocation failed");
+  }
+  *out = L;
+  return PP3_OK;
+}
+
+int pp3_learner_destroy(pp3_learner_t* L) {
+  if (!L) return PP3_OK;
+  (void)hipSetDevice(L->device);
+  for (int n = 0; n < 2; n++)
+    for (int w = 0; w < 4; w++) (void)hipFree(L->blob[n][w]);
+  float* ws[] = {L->x0, L->y, L->d[0], L->d[1], L->part, L->vs, L->adv, L->row_a, L->row_b, L->stats};
+  for (float* p : ws) (void)hipFree(p);
+  delete L;
+  return PP3_OK;
+}
+
+int pp3_learner_buffers(pp3_learner_t* L, int32_t net, int32_t which, float** ptr, int64_t* count) {
+  if (!L || !ptr || !count) return lerr(PP3_ERR_ARG, "pp3_learner_buffers: null argument");
+  if (net < 0 || net > 1 || which < 0 || which > 3)
+    return lerr(PP3_ERR_ARG, "pp3_learner_buffers: net is 0 (policy) or 1 (value), which 0 .. 3 (params, grads, m, v)");
+  *ptr = L->blob[net][which];
+  *count = (int64_t)L->net[net].count;
+  return PP3_OK;
+}
+
+int pp3_ppo_loss_grad(pp3_learner_t* L, int32_t nsteps, int32_t batch, int32_t num_envs, int32_t e0,
+                      const float* obs_all, const float* raw_action, const float* log_prob, const float* reward,
+                      const float* done, const float* truncation, const float* eps, const float* mean,
+                      const float* std_dev, float discount, float gae_lambda, float reward_scaling, float clip_eps,
+                      float entropy_cost, int32_t normalize_advantage, float* metrics_dev, void* stream) {
+  if (!L || !obs_all || !raw_action || !log_prob || !reward || !done || !truncation || !eps || !metrics_dev)
+    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: null argument");
+  if ((mean == nullptr) != (std_dev == nullptr))
+    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: mean and std are given together or not at all");
+  if (batch < 1 || nsteps < 1) return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: batch and nsteps must be >= 1");
+  if (e0 < 0 || num_envs < 1 || (int64_t)e0 + batch > num_envs)
+    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: the env range [e0, e0 + batch) must lie inside num_envs");
+  if (((int64_t)nsteps + 1) * batch > L->max_rows)
+    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: (nsteps + 1) * batch exceeds the learner's max_rows");
+  if (!isfinite(discount) || !isfinite(gae_lambda) || !isfinite(reward_scaling) || !isfinite(clip_eps) ||
+      !isfinite(entropy_cost))
+    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: the hyper-parameters must be finite");
+  if (!(clip_eps > 0.0f)) return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: clip_eps must be > 0");
+  LHIP(hipSetDevice(L->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int K = nsteps, B = batch, R = K * B, RV = (K + 1) * B;
+  const NetShape &ps = L->net[0], &vsn = L->net[1];
+  const size_t nx = (size_t)RV * ps.in_dim;
+  hipLaunchKernelGGL(gather_obs_kernel, dim3((unsigned)((nx + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0, st, obs_all,
+                     mean, std_dev, RV, B, num_envs, e0, ps.in_dim, L->x0);
+  RowArgs a{};
+  a.reward = reward; a.done = done; a.trunc = truncation; a.old_logp = log_prob; a.raw = raw_action; a.eps = eps;
+  a.vs = L->vs; a.adv = L->adv; a.row_a = L->row_a; a.row_b = L->row_b; a.stats = L->stats; a.metrics = metrics_dev;
+  a.K = K; a.B = B; a.N = num_envs; a.e0 = e0;
+  a.discount = discount; a.lambda = gae_lambda; a.reward_scaling = reward_scaling; a.clip_eps = clip_eps;
+  a.entropy_cost = entropy_cost; a.min_std = L->min_std; a.var_scale = L->var_scale;
+  a.normalize = normalize_advantage ? 1 : 0;
+  // the critic: baseline and bootstrap rows, targets, its gradient
+  a.values = forward(L, vsn, L->blob[1][0], RV, st);
+  a.dvalue = L->d[1];  // [R][1]: the value net's last delta
+  hipLaunchKernelGGL(value_head_kernel, dim3((B + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, st, a);
+  hipLaunchKernelGGL(value_stats_kernel, dim3(1), dim3(RED_BLOCK), 0, st, a);
+  // (backward writes its deltas to d[0], d[1], d[0], ..: each product reads one buffer and writes the other)
+  backward(L, vsn, L->blob[1][0], L->blob[1][1], a.dvalue, RV, R, st);
+  // the actor
+  a.logits = forward(L, ps, L->blob[0][0], R, st);
+  a.dlogits = L->d[1];
+  hipLaunchKernelGGL(policy_head_kernel, dim3((R + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, st, a);
+  hipLaunchKernelGGL(metrics_kernel, dim3(1), dim3(RED_BLOCK), 0, st, a);
+  backward(L, ps, L->blob[0][0], L->blob[0][1], a.dlogits, R, R, st);
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_adam_step(pp3_learner_t* L, float lr, float b1, float b2, float eps, float c1, float c2, void* stream) {
+  if (!L) return lerr(PP3_ERR_ARG, "pp3_adam_step: null learner");
+  if (!isfinite(lr) || !isfinite(b1) || !isfinite(b2) || !isfinite(eps) || !isfinite(c1) || !isfinite(c2))
+    return lerr(PP3_ERR_ARG, "pp3_adam_step: the hyper-parameters must be finite");
+  if (!(c1 > 0.0f) || !(c2 > 0.0f)) return lerr(PP3_ERR_ARG, "pp3_adam_step: c1 and c2 must be > 0");
+  LHIP(hipSetDevice(L->device));
+  for (int n = 0; n < 2; n++) {
+    const int64_t cnt = (int64_t)L->net[n].count;
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((cnt + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0, (hipStream_t)stream,
+                       L->blob[n][0], L->blob[n][1], L->blob[n][2], L->blob[n][3], cnt, lr, b1, b2, eps, c1, c2);
+  }
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_policy_load_params(pp3_policy_t* policy, const float* params_dev, int32_t in_dim, int32_t n_layers,
+                           const int32_t* out_dims, const float* mean_dev, const float* std_dev, void* stream) {
+  if (!policy || !params_dev || !out_dims) return lerr(PP3_ERR_ARG, "pp3_policy_load_params: null argument");
+  if ((mean_dev == nullptr) != (std_dev == nullptr))
+    return lerr(PP3_ERR_ARG, "pp3_policy_load_params: mean and std are given together or not at all");
+  const pp3pol::Net* net = pp3_policy_net(policy);
+  float* base = pp3_policy_weights(policy);
+  if (pp3_policy_device(policy) < 0 || !base)
+    return lerr(PP3_ERR_ARG, "pp3_policy_load_params: a host-side policy handle has no weights on a device");
+  if (net->n_layers != n_layers || net->in_dim != in_dim)
+    return lerr(PP3_ERR_ARG, "pp3_policy_load_params: the blob's shape differs from the handle's");
+  for (int l = 0; l < n_layers; l++)
+    if (net->layer[l].M != out_dims[l]) return lerr(PP3_ERR_ARG, "pp3_policy_load_params: the blob's shape differs from the handle's");
+  LHIP(hipSetDevice(pp3_policy_device(policy)));
+  size_t off = 0;
+  for (int l = 0; l < n_layers; l++) {
+    const pp3pol::Layer& Ly = net->layer[l];
+    RepackArgs r;
+    r.src = params_dev + off;
+    r.w = base + (Ly.w - net->layer[0].w);
+    r.b = base + (Ly.b - net->layer[0].w);
+    r.mean = l == 0 ? mean_dev : nullptr;
+    r.stdv = l == 0 ? std_dev : nullptr;
+    r.K = Ly.K; r.M = Ly.M; r.Mp = Ly.Mp; r.ngrp = Ly.ngrp; r.ntile = Ly.Mp / pp3pol::TILE;
+    const int total = r.ntile * r.ngrp * 256 + r.Mp;
+    hipLaunchKernelGGL(repack_kernel, dim3((total + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, (hipStream_t)stream, r);
+    off += (size_t)(Ly.K + 1) * Ly.M;
+  }
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+}  // extern "C"

@@ -343,5 +343,8 @@ __device__ __forceinline__ void mlp_tile(NetT& net, const float* __restrict__ ob
 // the device-side network of a policy handle (pp3_policy.hip; C++ linkage, not part of the C ABI)
 const pp3pol::Net* pp3_policy_net(const pp3_policy_t* p);
 int pp3_policy_device(const pp3_policy_t* p);
+// the handle's weight allocation, writable (pp3_learn.hip reloads it); net->layer[i].w / .b point into it,
+// layer 0's w at its start
+float* pp3_policy_weights(pp3_policy_t* p);
 // the policy's tanh-Gaussian head, if pp3_policy_set_distribution gave it one
 bool pp3_policy_distribution(const pp3_policy_t* p, float* min_std, float* var_scale);

@@ -191,6 +191,7 @@ bool pp3_policy_distribution(const pp3_policy_t* p, float* min_std, float* var_s
   return true;
 }
 int pp3_policy_device(const pp3_policy_t* p) { return p ? p->device : -1; }
+float* pp3_policy_weights(pp3_policy_t* p) { return p ? p->dev : nullptr; }
 
 extern "C" {
 

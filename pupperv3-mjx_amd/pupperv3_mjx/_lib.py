@@ -101,6 +101,19 @@ def load() -> C.CDLL:
         L.pp3_set_truncation_trajectory.restype = C.c_int
         L.pp3_gae.restype = C.c_int
         L.pp3_ppo_last_error.restype = C.c_char_p
+    if hasattr(L, "pp3_ppo_loss_grad"):  # (the PPO learner; absent from earlier builds run in kernel A/B)
+        f32 = C.c_float
+        L.pp3_learner_create.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, f32, f32, i64, C.POINTER(vp)]
+        L.pp3_learner_destroy.argtypes = [vp]
+        L.pp3_learner_buffers.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(i64)]
+        L.pp3_ppo_loss_grad.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32,
+                                        f32, i32, vp, vp]
+        L.pp3_adam_step.argtypes = [vp, f32, f32, f32, f32, f32, f32, vp]
+        L.pp3_policy_load_params.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+        for name in ("pp3_learner_create", "pp3_learner_destroy", "pp3_learner_buffers", "pp3_ppo_loss_grad",
+                     "pp3_adam_step", "pp3_policy_load_params"):
+            getattr(L, name).restype = C.c_int
+        L.pp3_learn_last_error.restype = C.c_char_p
     L.pp3_stream.argtypes = [vp]
     L.pp3_stream.restype = vp
     if hasattr(L, "pp3_event_create"):  # (absent from pre-round-5 builds run in kernel A/B: no host-API step there)
@@ -169,6 +182,8 @@ EXPORTED_SYMBOLS = (
     "pp3_rollout_policy", "pp3_rollout_policy_timed",
     "pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample", "pp3_rollout_policy_sample_timed",
     "pp3_set_truncation_trajectory", "pp3_gae", "pp3_ppo_last_error",
+    "pp3_learner_create", "pp3_learner_destroy", "pp3_learner_buffers", "pp3_ppo_loss_grad", "pp3_adam_step",
+    "pp3_policy_load_params", "pp3_learn_last_error",
     "pp3_stream", "pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy",
     "pp3_set_terrain", "pp3_terrain_slots",
     "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_comm_rank", "pp3_comm_world",

@@ -189,6 +189,27 @@ def sample_forward(policy: Dict[str, Any], obs, key, partitionable: bool = True)
     return np.tanh(raw), raw, normal_tanh_log_prob(logits, raw, dist["min_std"], dist["var_scale"]), logits
 
 
+def layers_blob(policy: Dict[str, Any]):
+    """(in_dim, out_dims int32[], activations int32[], f32 blob) of a converted dict's layers: the
+    arguments of pp3_policy_create (blob = per layer kernel [in][out] row-major, then bias [out])."""
+    in_dim = int(policy["in_shape"][1])
+    outs, acts, blob = [], [], []
+    k_in = in_dim
+    for layer in policy["layers"]:
+        k, b = np.asarray(layer["weights"][0], dtype=np.float32), np.asarray(layer["weights"][1], dtype=np.float32)
+        if k.shape != (k_in, b.shape[0]):
+            raise ValueError(f"layer kernel {k.shape} does not follow input width {k_in}")
+        name = layer["activation"].lower()
+        if name not in ACTIVATIONS:
+            raise ValueError(f"unsupported activation {name!r} (device: {sorted(ACTIVATIONS)})")
+        outs.append(b.shape[0])
+        acts.append(ACTIVATIONS[name])
+        blob += [k.ravel(), b]
+        k_in = b.shape[0]
+    return (in_dim, np.array(outs, dtype=np.int32), np.array(acts, dtype=np.int32),
+            np.ascontiguousarray(np.concatenate(blob), dtype=np.float32))
+
+
 DIST_NORMAL_TANH = 1  # PP3_DIST_NORMAL_TANH
 
 
@@ -201,32 +222,15 @@ class DevicePolicy:
         self._lib = _lib
         L = _lib.load()
         self._L = L
-        layers = policy["layers"]
-        in_dim = int(policy["in_shape"][1])
-        outs, acts, blob = [], [], []
-        k_in = in_dim
-        for layer in layers:
-            k, b = np.asarray(layer["weights"][0], dtype=np.float32), np.asarray(layer["weights"][1], dtype=np.float32)
-            if k.shape != (k_in, b.shape[0]):
-                raise ValueError(f"layer kernel {k.shape} does not follow input width {k_in}")
-            name = layer["activation"].lower()
-            if name not in ACTIVATIONS:
-                raise ValueError(f"unsupported activation {name!r} (device: {sorted(ACTIVATIONS)})")
-            outs.append(b.shape[0])
-            acts.append(ACTIVATIONS[name])
-            blob += [k.ravel(), b]
-            k_in = b.shape[0]
-        w = np.ascontiguousarray(np.concatenate(blob), dtype=np.float32)
-        o = np.array(outs, dtype=np.int32)
-        a = np.array(acts, dtype=np.int32)
+        in_dim, o, a, w = layers_blob(policy)
         h = C.c_void_p()
-        rc = L.pp3_policy_create(int(device), in_dim, len(layers), o.ctypes.data_as(C.c_void_p),
+        rc = L.pp3_policy_create(int(device), in_dim, len(o), o.ctypes.data_as(C.c_void_p),
                                  a.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), C.byref(h))
         if rc != 0:
             raise _lib.PupperHipError(L.pp3_policy_last_error().decode())
         self._h = h
         self.in_dim = in_dim
-        self.out_dim = int(outs[-1])
+        self.out_dim = int(o[-1])
         self.device = int(device)
         self.distribution = None
         dist = policy.get("distribution")

@@ -1,0 +1,171 @@
+"""Cost of the PPO learner step at the training shape (4096 envs, K = 20, after 200 warm-up steps),
+between device events, medians over `--repeat` alternating rounds with the run-to-run spread
+(min .. max) beside them:
+  (a) pp3_ppo_loss_grad + pp3_adam_step on one 256-env minibatch (5,120 rows) and on the whole
+      batch (81,920 rows), actor 72 -> 256 -> 128 -> 128 -> 24 and critic .. -> 1, elu;
+  (b) the reload of both handles (pp3_policy_load_params);
+  (c) reference 1: the sampled rollout of the same run (pp3_rollout_policy_sample_timed, K steps);
+  (d) reference 2, the yardstick for time: the same loss and gradient by torch eager autograd in
+      f32 on the same device and rows (tests/ppo_loss_ref.py `loss`, no optimiser step).
+One child process under a time limit.
+
+  python tools/ppo_learn_bench.py [--envs 4096 --warmup 200 --steps 20 --minibatch 256 --repeat 9 --timeout 300]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "pupperv3-mjx_amd"), os.path.join(ROOT, "tests")]
+
+
+def child(E: int, W: int, K: int, MB: int, R: int) -> None:
+    from collections import OrderedDict
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+
+    import bench
+    import ppo_loss_ref as ref
+    from pupperv3_mjx import MODEL_XML, _abi, _lib, export, ppo, rng
+    from pupperv3_mjx.environment import PupperV3Env
+
+    env = PupperV3Env(**bench.bench_kwargs(MODEL_XML), num_envs=E, device=0, pipeline_output=False)
+    L = env._L
+    raw_lib = _lib.load()  # (the HIP runtime's event calls resolve through the library's handle)
+    st = env.reset(np.ascontiguousarray(rng.split(rng.PRNGKey(0), E)))
+    _lib.check(L.pp3_set_auto_reset(env._h, 1000))
+    D = env.observation_size
+    rs = np.random.RandomState(7)
+
+    def net(last):
+        sizes = [D, 256, 128, 128, last]
+        layers = OrderedDict((f"hidden_{i}", {"kernel": rs.normal(scale=1 / np.sqrt(sizes[i]), size=(sizes[i], sizes[i + 1])),
+                                              "bias": np.zeros(sizes[i + 1])}) for i in range(len(sizes) - 1))
+        return (SimpleNamespace(mean=np.zeros(D), std=np.ones(D)), {"params": layers})
+
+    pdict = export.convert_training_params(net(2 * _abi.NU), "elu", 0.75, 5.0, 0.25, np.zeros(12), np.ones(12), -np.ones(12),
+                                           True, env._observation_history, 30.0, 30.0)
+    vdict = export.convert_value_params(net(1), "elu", env._observation_history)
+    normalizer = (rs.normal(scale=0.1, size=D).astype(np.float32), rs.uniform(0.5, 2.0, size=D).astype(np.float32))
+    learner = ppo.PPOLearner(pdict, vdict, normalizer=normalizer, max_rows=(K + 1) * E)
+    actor, critic = learner.make_policies()
+    key = np.array(rng.PRNGKey(1), dtype=np.uint32)
+    for w0 in range(0, W, K):  # (in unrolls of K: the trajectory each one returns stays small)
+        st, _, key = env.rollout_policy_sample(st, actor, min(K, W - w0), key)
+    st, batch, key = env.collect_ppo(st, actor, critic, K, key)
+    k_eps = rng.PRNGKey(2)
+    stream = C.c_void_p(L.pp3_stream(env._h))
+    ms = C.c_float()
+    ev = [C.c_void_p(), C.c_void_p()]
+    for e in ev:
+        assert raw_lib.hipEventCreate(C.byref(e)) == 0
+
+    def timed(fn):
+        assert raw_lib.hipEventRecord(ev[0], stream) == 0
+        fn()
+        assert raw_lib.hipEventRecord(ev[1], stream) == 0
+        assert raw_lib.hipEventSynchronize(ev[1]) == 0
+        assert raw_lib.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
+        return ms.value
+
+    def step(B):
+        learner.loss_and_grad(env, 0, B, k_eps)
+        learner.adam_step(3e-4)
+
+    # the same rows for torch: its own copies on the same device
+    dev = torch.device("cuda:0")
+    eps = rng.normal(k_eps, (K, E, 12), env._partitionable)
+    host = dict(obs_all=np.concatenate([batch["observation"], batch["obs"][-1:]]), raw_action=batch["raw_action"],
+                log_prob=batch["log_prob"], reward=batch["reward"], done=batch["done"], truncation=batch["truncation"], eps=eps)
+    tb = {B: {k: torch.tensor(np.ascontiguousarray(v[:, :B]), device=dev) for k, v in host.items()} for B in (MB, E)}
+    tnorm = tuple(torch.tensor(a, device=dev) for a in normalizer)
+    cur = learner.params()
+    tparams = {name: [(torch.tensor(k, device=dev, requires_grad=True), torch.tensor(b, device=dev, requires_grad=True))
+                      for k, b in cur[name]] for name in ("policy", "value")}
+    flat = [p for name in ("policy", "value") for kb in tparams[name] for p in kb]
+    tev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def torch_step(B):
+        tev[0].record()
+        m, _ = ref.loss(tparams["policy"], tparams["value"], "elu", tb[B], torch.float32, tnorm, **ppo.HPARAMS)
+        grads = torch.autograd.grad(m["total_loss"], flat)
+        tev[1].record()
+        tev[1].synchronize()
+        return tev[0].elapsed_time(tev[1]), float(m["total_loss"]), grads
+
+    # parity of what is timed: the two compute the same loss
+    learner.loss_and_grad(env, 0, MB, k_eps)
+    ours = learner.metrics()["total_loss"]
+    _, theirs, _ = torch_step(MB)
+    act, raw = _lib.DeviceBuffer(4 * K * E * 12), _lib.DeviceBuffer(4 * K * E * 12)
+    logp, rew, done = (_lib.DeviceBuffer(4 * K * E) for _ in range(3))
+    obs = _lib.DeviceBuffer(4 * K * E * D)
+    kin, kout = np.array(key, dtype=np.uint32), np.zeros(2, dtype=np.uint32)
+
+    def rollout():
+        _lib.check(L.pp3_rollout_policy_sample_timed(env._h, actor._h, K, kin.ctypes.data_as(C.c_void_p),
+                                                     kout.ctypes.data_as(C.c_void_p), act.ptr, raw.ptr, logp.ptr, rew.ptr,
+                                                     done.ptr, obs.ptr, C.byref(ms)))
+        return ms.value
+
+    names = ("learn_minibatch_ms", "learn_batch_ms", "reload_ms", "rollout_ms", "torch_minibatch_ms", "torch_batch_ms")
+    out = {k: [] for k in names}
+    for r in range(R + 2):  # rounds 0 and 1 warm every shape up
+        got = dict(learn_minibatch_ms=timed(lambda: step(MB)), torch_minibatch_ms=torch_step(MB)[0],
+                   learn_batch_ms=timed(lambda: step(E)), torch_batch_ms=torch_step(E)[0],
+                   reload_ms=timed(lambda: learner.sync(actor, critic)), rollout_ms=rollout())
+        if r >= 2:
+            for k, v in got.items():
+                out[k].append(round(v, 4))
+    med = {k: sorted(x)[len(x) // 2] for k, x in out.items()}
+    spread = {k: [min(x), max(x)] for k, x in out.items()}
+    final = learner.metrics()
+    print(json.dumps({"envs": E, "warmup": W, "steps": K, "minibatch_envs": MB, "rounds": R,
+                      "rows": {"minibatch": K * MB, "batch": K * E}, "median_ms": med, "min_max_ms": spread,
+                      "learn_over_torch": {"minibatch": round(med["learn_minibatch_ms"] / med["torch_minibatch_ms"], 3),
+                                           "batch": round(med["learn_batch_ms"] / med["torch_batch_ms"], 3)},
+                      "learn_batch_share_of_rollout": round(med["learn_batch_ms"] / med["rollout_ms"], 3),
+                      "first_total_loss": {"learner": ours, "torch": theirs},
+                      "losses_finite": bool(all(np.isfinite(v) for v in final.values()))}), flush=True)
+    for e in ev:
+        raw_lib.hipEventDestroy(e)
+    actor.close()
+    critic.close()
+    learner.close()
+    env.close()
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--minibatch", type=int, default=256, help="envs of the small minibatch")
+    ap.add_argument("--repeat", type=int, default=9, help="timed rounds (medians and min .. max are reported)")
+    ap.add_argument("--timeout", type=float, default=300.0, help="seconds for the child process")
+    ap.add_argument("--child", action="store_true")
+    args = ap.parse_args()
+    if args.child:
+        child(args.envs, args.warmup, args.steps, args.minibatch, args.repeat)
+        return 0
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--envs", str(args.envs), "--warmup", str(args.warmup),
+           "--steps", str(args.steps), "--minibatch", str(args.minibatch), "--repeat", str(args.repeat)]
+    try:
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
+    except subprocess.TimeoutExpired:
+        print(f"no result within {args.timeout} s", file=sys.stderr)
+        return 124
+    if out.returncode != 0:
+        sys.stderr.write(out.stderr[-2000:])
+        return out.returncode
+    print(out.stdout.strip().split("\n")[-1], flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
