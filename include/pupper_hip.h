@@ -668,6 +668,54 @@ int pp3_adam_step(pp3_learner_t* learner, float lr, float b1, float b2, float ep
  * unchanged; work queued on `stream` before this call sees the old weights. */
 int pp3_policy_load_params(pp3_policy_t* policy, const float* params_dev, int32_t in_dim, int32_t n_layers,
                            const int32_t* out_dims, const float* mean_dev, const float* std_dev, void* stream);
+
+/* ---- PPO learner: running normaliser, shuffled minibatches, gradient clip (additive; ABI stays 2) ----
+ * What [ext] brax 0.12.1 training_step does around compute_ppo_loss, restated from memory (brax
+ * running_statistics.update, jax.random.permutation in sgd_step, optax.clip_by_global_norm); what is
+ * written here is the contract.  f32, fixed-order sums, no atomics: a call repeated on the same
+ * inputs gives the same bits.  Errors are PP3_ERR_ARG through pp3_learn_last_error() before
+ * anything is launched, outputs untouched.
+ *
+ * pp3_learner_normalizer_update: one running_statistics.update of (mean, summed_variance, std_dev),
+ * each [in_dim] on the device and updated in place, from obs [rows][in_dim] (contiguous; in_dim is
+ * the learner's).  count_new is the old count plus rows, kept by the host as an integer and passed
+ * rounded to f32 (as Adam's c1 and c2 are).  Per column k:
+ *   d_old[r] = obs[r][k] - mean[k]
+ *   mean'[k] = mean[k] + (sum_r d_old[r]) / count_new
+ *   sv'[k]   = sv[k] + sum_r d_old[r] * (obs[r][k] - mean'[k])
+ *   std'[k]  = clip(sqrt(max(sv'[k], 0) / count_new), std_min, std_max)
+ * both quotients correctly rounded.  Brax starts from count 0, mean 0, summed_variance 0, std 1, with
+ * std_min = 1e-6 and std_max = 1e6.  The rows of a collect_ppo batch are rows 0 .. K-1 of its
+ * [K+1][N][in_dim] observation buffer: rows = K N from its base; the bootstrap row K is not read.
+ * Two sweeps over obs (the second needs mean').  The rows are summed in 1024 equal ranges (of
+ * ceil(rows / 1024) rows) into a workspace the learner owns, then the ranges; the order depends on
+ * (rows, in_dim) alone and rows is not bounded by max_rows.
+ * PP3_ERR_ARG: a null pointer, rows < 1, count_new not finite or < rows, std_min or std_max not
+ * finite, or not 0 < std_min <= std_max. */
+int pp3_learner_normalizer_update(pp3_learner_t* learner, const float* obs, int64_t rows, float count_new,
+                                  float std_min, float std_max, float* mean, float* summed_variance, float* std_dev,
+                                  void* stream);
+/* Shuffled minibatches.  pp3_learner_set_env_index validates on the host that num_envs >= 1 and
+ * every entry of index_host[num_envs] lies in [0, num_envs) (else PP3_ERR_ARG and nothing is copied:
+ * an invalid index never reaches a kernel), then copies it into a device buffer the learner owns,
+ * in stream order: work queued on `stream` earlier keeps the old index, and index_host is free
+ * again on return.  pp3_ppo_loss_grad_indexed is pp3_ppo_loss_grad (same parameters, results and
+ * errors) except that row e of the minibatch reads env index[e0 + e] of every batch array, eps
+ * included, where pp3_ppo_loss_grad reads env e0 + e; further PP3_ERR_ARG: no index set, or the
+ * index's num_envs differs from the call's.  The index need not be a permutation. */
+int pp3_learner_set_env_index(pp3_learner_t* learner, const int32_t* index_host, int32_t num_envs, void* stream);
+int pp3_ppo_loss_grad_indexed(pp3_learner_t* learner, int32_t nsteps, int32_t batch, int32_t num_envs, int32_t e0,
+                              const float* obs_all, const float* raw_action, const float* log_prob,
+                              const float* reward, const float* done, const float* truncation, const float* eps,
+                              const float* mean, const float* std_dev, float discount, float gae_lambda,
+                              float reward_scaling, float clip_eps, float entropy_cost, int32_t normalize_advantage,
+                              float* metrics_dev, void* stream);
+/* optax.clip_by_global_norm on the learner's gradient blobs, between the loss and pp3_adam_step:
+ *   s = sum of g^2 over the policy blob, then the value blob (chunks of 4096 elements, then the
+ *   chunks, each in a fixed order);  norm = sqrt(s), written to norm_dev f32[1] when it is not NULL;
+ *   norm < max_norm: the gradients stay bit for bit as they were;  else g <- (g / norm) * max_norm.
+ * PP3_ERR_ARG: a null learner, max_norm not finite or <= 0. */
+int pp3_grad_clip(pp3_learner_t* learner, float max_norm, float* norm_dev, void* stream);
 const char* pp3_learn_last_error(void);
 
 /* ---------------------------------------------------------------------------------------

@@ -15,9 +15,16 @@
 // indices checked: rows past R and columns past a layer's width read as zero and are never
 // dereferenced.  Nothing is accumulated with atomics: every sum has one fixed order, so a call
 // repeats bit for bit.
+//
+// Around the loss (Brax's training_step beyond compute_ppo_loss): the running normaliser
+// (pp3_learner_normalizer_update: two coalesced sweeps over the observation matrix, each thread on one
+// column, per-row-range partials, a single-block finish), shuffled minibatches (a validated env index
+// the three batch-reading kernels read through; NULL is the contiguous range) and the global-norm
+// gradient clip (pp3_grad_clip), all with the same fixed-order sums.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
@@ -146,15 +153,18 @@ __global__ __launch_bounds__(NTHREAD) void sum_partials_kernel(const float* __re
   grad[i] = s;
 }
 
-// x0[t * B + e][k] = (obs_all[t][e0 + e][k] - mean[k]) / std[k], t <= K
+// x0[t * B + e][k] = (obs_all[t][env(e)][k] - mean[k]) / std[k], t <= K; env(e) = e0 + e, or
+// index[e0 + e] when there is an index
 __global__ __launch_bounds__(NTHREAD) void gather_obs_kernel(const float* __restrict__ obs, const float* __restrict__ mean,
                                                              const float* __restrict__ stdv, int rows, int B, int N,
-                                                             int e0, int in_dim, float* __restrict__ x0) {
+                                                             int e0, const int32_t* __restrict__ index, int in_dim,
+                                                             float* __restrict__ x0) {
   const size_t idx = (size_t)blockIdx.x * NTHREAD + threadIdx.x;
   if (idx >= (size_t)rows * in_dim) return;
   const int r = (int)(idx / in_dim), k = (int)(idx - (size_t)r * in_dim);
   const int t = r / B, e = r - t * B;
-  float v = obs[((size_t)t * N + e0 + e) * in_dim + k];
+  const int env = index ? index[e0 + e] : e0 + e;
+  float v = obs[((size_t)t * N + env) * in_dim + k];
   if (mean) v = div_rn(v - mean[k], stdv[k]);
   x0[idx] = v;
 }
@@ -184,6 +194,7 @@ struct RowArgs {
   float* stats;         // [4]: v_loss, adv mean, adv std
   float* metrics;       // [4]: total, policy, value, entropy
   int K, B, N, e0;
+  const int32_t* index;  // null: row e of the minibatch is env e0 + e; else env index[e0 + e]
   float discount, lambda, reward_scaling, clip_eps, entropy_cost, min_std, var_scale;
   int normalize;
 };
@@ -197,8 +208,9 @@ __global__ __launch_bounds__(NTHREAD) void value_head_kernel(RowArgs a) {
   const int R = a.K * a.B;
   float vnext = a.values[(size_t)a.K * a.B + e];
   float vsnext = vnext, acc = 0.0f;
+  const int env = a.index ? a.index[a.e0 + e] : a.e0 + e;
   for (int t = a.K - 1; t >= 0; t--) {
-    const size_t at = (size_t)t * a.N + a.e0 + e;
+    const size_t at = (size_t)t * a.N + env;
     const int r = t * a.B + e;
     const float v = a.values[r];
     const float tm = 1.0f - a.trunc[at];
@@ -252,7 +264,7 @@ __global__ __launch_bounds__(NTHREAD) void policy_head_kernel(RowArgs a) {
   const int R = a.K * a.B;
   if (r >= R) return;
   const int t = r / a.B, e = r - t * a.B;
-  const size_t at = (size_t)t * a.N + a.e0 + e;
+  const size_t at = (size_t)t * a.N + (a.index ? a.index[a.e0 + e] : a.e0 + e);
   const float* lg = a.logits + (size_t)r * 2 * NU;
   const float* raw = a.raw + at * NU;
   const float* eps = a.eps + at * NU;
@@ -324,6 +336,154 @@ __global__ __launch_bounds__(NTHREAD) void adam_kernel(float* __restrict__ p, co
   p[i] = p[i] - (lr * (mi / c1)) / (sqrtf(vi / c2) + eps);
 }
 
+// ---- the running normaliser (running_statistics.update) ----
+// Column sums over the row-major obs [rows][in_dim] in two levels.  The rows are cut into
+// NORM_RANGES equal ranges of rpr = ceil(rows / NORM_RANGES) rows (the last ones short or empty; empty
+// ones are not launched); a workgroup sums one range, the single finishing workgroup the ranges.
+// In both, a workgroup of T threads is laid out as G = T / w groups of w = min(in_dim, W) columns:
+// thread (g, k) stays on column c0 + k and adds entries g, g + G, .. ascending, so one trip of the
+// workgroup reads G consecutive rows (G w consecutive floats when w = in_dim); the G sums of a column
+// are then added in LDS in group order; columns past w take further trips (c0 += w).  The order
+// depends on (rows, in_dim) alone.
+constexpr int NORM_RANGES = 1024;
+constexpr int NORM_FIN_COLS = 64;  // W of the finish (the sweep's is its workgroup: NTHREAD)
+
+// PASS 0: part[range][k] = sum_r (obs[r][k] - mean[k])
+// PASS 1: part[range][k] = sum_r (obs[r][k] - mean[k]) * (obs[r][k] - mean_new[k])
+template <int PASS>
+__global__ __launch_bounds__(NTHREAD) void norm_sweep_kernel(const float* __restrict__ obs, int64_t rows, int64_t rpr,
+                                                             int in_dim, const float* __restrict__ mean,
+                                                             const float* __restrict__ mean_new,
+                                                             float* __restrict__ part) {
+  __shared__ float sh[NTHREAD];
+  const int tid = threadIdx.x;
+  const int w = min(in_dim, NTHREAD), G = NTHREAD / w;
+  const int g = tid / w, kk = tid - g * w;
+  const int64_t r0 = (int64_t)blockIdx.x * rpr;
+  const int64_t r1 = min(rows, r0 + rpr);
+  for (int c0 = 0; c0 < in_dim; c0 += w) {
+    const int k = c0 + kk;
+    float s = 0.0f;
+    if (g < G && k < in_dim) {
+      const float m0 = mean[k];
+      const float m1 = PASS ? mean_new[k] : 0.0f;
+#pragma unroll 4
+      for (int64_t r = r0 + g; r < r1; r += G) {
+        const float x = obs[(size_t)r * (size_t)in_dim + k];
+        const float d = x - m0;
+        s += PASS ? d * (x - m1) : d;
+      }
+    }
+    __syncthreads();
+    sh[tid] = s;
+    __syncthreads();
+    if (g == 0 && k < in_dim) {
+      for (int j = 1; j < G; j++) s += sh[j * w + kk];
+      part[(size_t)blockIdx.x * in_dim + k] = s;
+    }
+  }
+}
+
+// S[k] = sum over the nr ranges of part[range][k], then
+// PASS 0: mean_new[k] = mean[k] + S / count
+// PASS 1: sv[k] += S; std[k] = clip(sqrt(max(sv[k], 0) / count), std_min, std_max); mean[k] = mean_new[k]
+template <int PASS>
+__global__ __launch_bounds__(RED_BLOCK) void norm_finish_kernel(const float* __restrict__ part, int nr, int in_dim,
+                                                                float count, float std_min, float std_max,
+                                                                float* __restrict__ mean, float* __restrict__ mean_new,
+                                                                float* __restrict__ sv, float* __restrict__ stdv) {
+  __shared__ float sh[RED_BLOCK];
+  const int tid = threadIdx.x;
+  const int w = min(in_dim, NORM_FIN_COLS), G = RED_BLOCK / w;
+  const int g = tid / w, kk = tid - g * w;
+  for (int c0 = 0; c0 < in_dim; c0 += w) {
+    const int k = c0 + kk;
+    float s = 0.0f;
+    if (g < G && k < in_dim) {
+      // (unrolled so that the loads of 16 partials are in flight together; the adds keep their order)
+#pragma unroll 16
+      for (int r = g; r < nr; r += G) s += part[(size_t)r * in_dim + k];
+    }
+    __syncthreads();
+    sh[tid] = s;
+    __syncthreads();
+    if (g == 0 && k < in_dim) {
+      for (int j = 1; j < G; j++) s += sh[j * w + kk];
+      if (PASS == 0) {
+        mean_new[k] = mean[k] + div_rn(s, count);
+      } else {
+        const float v = sv[k] + s;
+        sv[k] = v;
+        // (the build's fast sqrt is within 1 ulp; one residual step, as in div_rn)
+        const float q = div_rn(fmaxf(v, 0.0f), count);
+        float sd = sqrtf(q);
+        if (sd > 0.0f && sd < INFINITY) sd = fmaf(fmaf(-sd, sd, q), 0.5f / sd, sd);
+        stdv[k] = fminf(fmaxf(sd, std_min), std_max);
+        mean[k] = mean_new[k];
+      }
+    }
+  }
+}
+
+// ---- the global-norm clip (optax.clip_by_global_norm) ----
+// The gradient blobs as one array, policy then value: element i is g0[i] for i < n0, else g1[i - n0].
+constexpr int CLIP_CHUNK = 16 * NTHREAD;  // elements per workgroup of both clip kernels
+
+// the NTHREAD values of a workgroup in a binary tree in LDS; all threads get the result
+__device__ __forceinline__ float tree_sum(float v, float* sh) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  sh[tid] = v;
+  __syncthreads();
+  for (int s = NTHREAD / 2; s > 0; s >>= 1) {
+    if (tid < s) sh[tid] += sh[tid + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// part[b] = sum of g^2 over chunk b: thread i adds elements i, i + NTHREAD, .. ascending, then the tree
+__global__ __launch_bounds__(NTHREAD) void grad_sumsq_kernel(const float* __restrict__ g0, int64_t n0,
+                                                             const float* __restrict__ g1, int64_t n,
+                                                             float* __restrict__ part) {
+  __shared__ float sh[NTHREAD];
+  const int64_t base = (int64_t)blockIdx.x * CLIP_CHUNK + threadIdx.x;
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < CLIP_CHUNK / NTHREAD; j++) {
+    const int64_t i = base + (int64_t)j * NTHREAD;
+    if (i < n) {
+      const float v = i < n0 ? g0[i] : g1[i - n0];
+      s += v * v;
+    }
+  }
+  s = tree_sum(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// Every workgroup adds the nblk partials in the same order (thread i: partials i, i + NTHREAD, ..,
+// then the tree), so all hold the same norm; below max_norm nothing is stored.
+__global__ __launch_bounds__(NTHREAD) void grad_clip_kernel(float* __restrict__ g0, int64_t n0, float* __restrict__ g1,
+                                                            int64_t n, const float* __restrict__ part, int nblk,
+                                                            float max_norm, float* __restrict__ norm_out) {
+#pragma clang fp contract(off)
+  __shared__ float sh[NTHREAD];
+  float s = 0.0f;
+  for (int b = threadIdx.x; b < nblk; b += NTHREAD) s += part[b];
+  const float norm = sqrtf(tree_sum(s, sh));
+  if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) *norm_out = norm;
+  if (norm < max_norm) return;
+  const int64_t base = (int64_t)blockIdx.x * CLIP_CHUNK + threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < CLIP_CHUNK / NTHREAD; j++) {
+    const int64_t i = base + (int64_t)j * NTHREAD;
+    if (i < n) {
+      float* p = i < n0 ? g0 + i : g1 + (i - n0);
+      *p = (*p / norm) * max_norm;
+    }
+  }
+}
+
 // One layer of a handle's fragment-order weights from the blob (pp3_policy_create's packing);
 // layer 0 folded with the normaliser when there is one.
 struct RepackArgs {
@@ -385,6 +545,16 @@ struct pp3_learner {
   float* d[2];        // deltas, ping-pong, [max_rows][max width]
   float* part;        // weight-gradient partials [chunks][(K + 1) M]
   float *vs, *adv, *row_a, *row_b, *stats;
+  float* norm_part;  // the normaliser's partials [NORM_RANGES][in_dim]
+  float* norm_mean;  // [in_dim] mean' between the two sweeps
+  float* clip_part;  // [clip_blocks] the clip's partial sums of squares
+  int clip_blocks;
+  // The env index: the device copy, and two pinned staging blocks taken in turn, each with the event
+  // of the copy that last read it (pp3_learner_set_env_index waits for that one before refilling).
+  int32_t* idx_dev;
+  int32_t* idx_host[2];
+  hipEvent_t idx_ev[2];
+  int idx_cap, idx_n, idx_turn;  // allocated entries; entries set (0: none); the next staging block
 };
 
 static thread_local std::string g_lerr;
@@ -482,6 +652,73 @@ static void backward(pp3_learner* L, const NetShape& s, const float* params, flo
   }
 }
 
+// waits for the copies still reading the staging blocks, then frees the index's three allocations
+static void free_env_index(pp3_learner* L) {
+  for (int i = 0; i < 2; i++) {
+    if (L->idx_ev[i]) {
+      (void)hipEventSynchronize(L->idx_ev[i]);
+      (void)hipEventDestroy(L->idx_ev[i]);
+    }
+    if (L->idx_host[i]) (void)hipHostFree(L->idx_host[i]);
+    L->idx_ev[i] = nullptr;
+    L->idx_host[i] = nullptr;
+  }
+  if (L->idx_dev) (void)hipFree(L->idx_dev);
+  L->idx_dev = nullptr;
+  L->idx_cap = L->idx_n = 0;
+}
+
+// pp3_ppo_loss_grad (index null) and pp3_ppo_loss_grad_indexed: one path; `fn` names the entry point
+static int loss_grad(const char* fn, pp3_learner* L, int32_t nsteps, int32_t batch, int32_t num_envs, int32_t e0,
+                     const int32_t* index, const float* obs_all, const float* raw_action, const float* log_prob,
+                     const float* reward, const float* done, const float* truncation, const float* eps,
+                     const float* mean, const float* std_dev, float discount, float gae_lambda, float reward_scaling,
+                     float clip_eps, float entropy_cost, int32_t normalize_advantage, float* metrics_dev, void* stream) {
+  const std::string f(fn);
+  if (!L || !obs_all || !raw_action || !log_prob || !reward || !done || !truncation || !eps || !metrics_dev)
+    return lerr(PP3_ERR_ARG, f + ": null argument");
+  if ((mean == nullptr) != (std_dev == nullptr))
+    return lerr(PP3_ERR_ARG, f + ": mean and std are given together or not at all");
+  if (batch < 1 || nsteps < 1) return lerr(PP3_ERR_ARG, f + ": batch and nsteps must be >= 1");
+  if (e0 < 0 || num_envs < 1 || (int64_t)e0 + batch > num_envs)
+    return lerr(PP3_ERR_ARG, f + ": the env range [e0, e0 + batch) must lie inside num_envs");
+  if (((int64_t)nsteps + 1) * batch > L->max_rows)
+    return lerr(PP3_ERR_ARG, f + ": (nsteps + 1) * batch exceeds the learner's max_rows");
+  if (!isfinite(discount) || !isfinite(gae_lambda) || !isfinite(reward_scaling) || !isfinite(clip_eps) ||
+      !isfinite(entropy_cost))
+    return lerr(PP3_ERR_ARG, f + ": the hyper-parameters must be finite");
+  if (!(clip_eps > 0.0f)) return lerr(PP3_ERR_ARG, f + ": clip_eps must be > 0");
+  LHIP(hipSetDevice(L->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int K = nsteps, B = batch, R = K * B, RV = (K + 1) * B;
+  const NetShape &ps = L->net[0], &vsn = L->net[1];
+  const size_t nx = (size_t)RV * ps.in_dim;
+  hipLaunchKernelGGL(gather_obs_kernel, dim3((unsigned)((nx + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0, st, obs_all,
+                     mean, std_dev, RV, B, num_envs, e0, index, ps.in_dim, L->x0);
+  RowArgs a{};
+  a.reward = reward; a.done = done; a.trunc = truncation; a.old_logp = log_prob; a.raw = raw_action; a.eps = eps;
+  a.vs = L->vs; a.adv = L->adv; a.row_a = L->row_a; a.row_b = L->row_b; a.stats = L->stats; a.metrics = metrics_dev;
+  a.K = K; a.B = B; a.N = num_envs; a.e0 = e0; a.index = index;
+  a.discount = discount; a.lambda = gae_lambda; a.reward_scaling = reward_scaling; a.clip_eps = clip_eps;
+  a.entropy_cost = entropy_cost; a.min_std = L->min_std; a.var_scale = L->var_scale;
+  a.normalize = normalize_advantage ? 1 : 0;
+  // the critic: baseline and bootstrap rows, targets, its gradient
+  a.values = forward(L, vsn, L->blob[1][0], RV, st);
+  a.dvalue = L->d[1];  // [R][1]: the value net's last delta
+  hipLaunchKernelGGL(value_head_kernel, dim3((B + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, st, a);
+  hipLaunchKernelGGL(value_stats_kernel, dim3(1), dim3(RED_BLOCK), 0, st, a);
+  // (backward writes its deltas to d[0], d[1], d[0], ..: each product reads one buffer and writes the other)
+  backward(L, vsn, L->blob[1][0], L->blob[1][1], a.dvalue, RV, R, st);
+  // the actor
+  a.logits = forward(L, ps, L->blob[0][0], R, st);
+  a.dlogits = L->d[1];
+  hipLaunchKernelGGL(policy_head_kernel, dim3((R + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, st, a);
+  hipLaunchKernelGGL(metrics_kernel, dim3(1), dim3(RED_BLOCK), 0, st, a);
+  backward(L, ps, L->blob[0][0], L->blob[0][1], a.dlogits, R, R, st);
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
 extern "C" {
 
 const char* pp3_learn_last_error(void) { return g_lerr.c_str(); }
@@ -536,6 +773,10 @@ int pp3_learner_create(int32_t device, int32_t in_dim, int32_t policy_layers, co
   alloc(&L->row_a, rows);
   alloc(&L->row_b, rows);
   alloc(&L->stats, 4);
+  alloc(&L->norm_part, (size_t)NORM_RANGES * in_dim);
+  alloc(&L->norm_mean, in_dim);
+  L->clip_blocks = (int)((ps.count + vs.count + CLIP_CHUNK - 1) / CLIP_CHUNK);
+  alloc(&L->clip_part, L->clip_blocks);
   ok = ok && hipMemcpy(L->blob[0][0], policy_weights, ps.count * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
   ok = ok && hipMemcpy(L->blob[1][0], value_weights, vs.count * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
@@ -551,8 +792,10 @@ int pp3_learner_destroy(pp3_learner_t* L) {
   (void)hipSetDevice(L->device);
   for (int n = 0; n < 2; n++)
     for (int w = 0; w < 4; w++) (void)hipFree(L->blob[n][w]);
-  float* ws[] = {L->x0, L->y, L->d[0], L->d[1], L->part, L->vs, L->adv, L->row_a, L->row_b, L->stats};
+  float* ws[] = {L->x0, L->y, L->d[0], L->d[1], L->part, L->vs, L->adv, L->row_a, L->row_b, L->stats,
+                 L->norm_part, L->norm_mean, L->clip_part};
   for (float* p : ws) (void)hipFree(p);
+  free_env_index(L);
   delete L;
   return PP3_OK;
 }
@@ -571,46 +814,93 @@ int pp3_ppo_loss_grad(pp3_learner_t* L, int32_t nsteps, int32_t batch, int32_t n
                       const float* done, const float* truncation, const float* eps, const float* mean,
                       const float* std_dev, float discount, float gae_lambda, float reward_scaling, float clip_eps,
                       float entropy_cost, int32_t normalize_advantage, float* metrics_dev, void* stream) {
-  if (!L || !obs_all || !raw_action || !log_prob || !reward || !done || !truncation || !eps || !metrics_dev)
-    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: null argument");
-  if ((mean == nullptr) != (std_dev == nullptr))
-    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: mean and std are given together or not at all");
-  if (batch < 1 || nsteps < 1) return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: batch and nsteps must be >= 1");
-  if (e0 < 0 || num_envs < 1 || (int64_t)e0 + batch > num_envs)
-    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: the env range [e0, e0 + batch) must lie inside num_envs");
-  if (((int64_t)nsteps + 1) * batch > L->max_rows)
-    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: (nsteps + 1) * batch exceeds the learner's max_rows");
-  if (!isfinite(discount) || !isfinite(gae_lambda) || !isfinite(reward_scaling) || !isfinite(clip_eps) ||
-      !isfinite(entropy_cost))
-    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: the hyper-parameters must be finite");
-  if (!(clip_eps > 0.0f)) return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad: clip_eps must be > 0");
+  return loss_grad("pp3_ppo_loss_grad", L, nsteps, batch, num_envs, e0, nullptr, obs_all, raw_action, log_prob, reward,
+                   done, truncation, eps, mean, std_dev, discount, gae_lambda, reward_scaling, clip_eps, entropy_cost,
+                   normalize_advantage, metrics_dev, stream);
+}
+
+int pp3_learner_set_env_index(pp3_learner_t* L, const int32_t* index_host, int32_t num_envs, void* stream) {
+  if (!L || !index_host) return lerr(PP3_ERR_ARG, "pp3_learner_set_env_index: null argument");
+  if (num_envs < 1) return lerr(PP3_ERR_ARG, "pp3_learner_set_env_index: num_envs must be >= 1");
+  for (int32_t i = 0; i < num_envs; i++)
+    if (index_host[i] < 0 || index_host[i] >= num_envs)
+      return lerr(PP3_ERR_ARG, "pp3_learner_set_env_index: entry " + std::to_string(i) + " is outside [0, num_envs)");
+  LHIP(hipSetDevice(L->device));
+  if (num_envs > L->idx_cap) {  // (hipFree waits for the queued work that reads the old copy)
+    free_env_index(L);
+    const size_t bytes = (size_t)num_envs * sizeof(int32_t);
+    bool ok = hipMalloc(&L->idx_dev, bytes) == hipSuccess;
+    for (int i = 0; i < 2; i++)
+      ok = ok && hipHostMalloc(&L->idx_host[i], bytes, hipHostMallocDefault) == hipSuccess &&
+           hipEventCreateWithFlags(&L->idx_ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      free_env_index(L);
+      return lerr(PP3_ERR_NOMEM, "pp3_learner_set_env_index: allocation failed");
+    }
+    L->idx_cap = num_envs;
+  }
+  const int s = L->idx_turn;
+  LHIP(hipEventSynchronize(L->idx_ev[s]));  // the copy that last read this staging block (none: returns at once)
+  const size_t bytes = (size_t)num_envs * sizeof(int32_t);
+  memcpy(L->idx_host[s], index_host, bytes);
+  LHIP(hipMemcpyAsync(L->idx_dev, L->idx_host[s], bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  LHIP(hipEventRecord(L->idx_ev[s], (hipStream_t)stream));
+  L->idx_turn = s ^ 1;
+  L->idx_n = num_envs;
+  return PP3_OK;
+}
+
+int pp3_ppo_loss_grad_indexed(pp3_learner_t* L, int32_t nsteps, int32_t batch, int32_t num_envs, int32_t e0,
+                              const float* obs_all, const float* raw_action, const float* log_prob,
+                              const float* reward, const float* done, const float* truncation, const float* eps,
+                              const float* mean, const float* std_dev, float discount, float gae_lambda,
+                              float reward_scaling, float clip_eps, float entropy_cost, int32_t normalize_advantage,
+                              float* metrics_dev, void* stream) {
+  if (L && L->idx_n == 0)
+    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad_indexed: no env index is set (pp3_learner_set_env_index)");
+  if (L && L->idx_n != num_envs)
+    return lerr(PP3_ERR_ARG, "pp3_ppo_loss_grad_indexed: the env index was set for another num_envs");
+  return loss_grad("pp3_ppo_loss_grad_indexed", L, nsteps, batch, num_envs, e0, L ? L->idx_dev : nullptr, obs_all,
+                   raw_action, log_prob, reward, done, truncation, eps, mean, std_dev, discount, gae_lambda,
+                   reward_scaling, clip_eps, entropy_cost, normalize_advantage, metrics_dev, stream);
+}
+
+int pp3_learner_normalizer_update(pp3_learner_t* L, const float* obs, int64_t rows, float count_new, float std_min,
+                                  float std_max, float* mean, float* summed_variance, float* std_dev, void* stream) {
+  if (!L || !obs || !mean || !summed_variance || !std_dev)
+    return lerr(PP3_ERR_ARG, "pp3_learner_normalizer_update: null argument");
+  if (rows < 1) return lerr(PP3_ERR_ARG, "pp3_learner_normalizer_update: rows must be >= 1");
+  if (!isfinite(count_new) || count_new < (float)rows)
+    return lerr(PP3_ERR_ARG, "pp3_learner_normalizer_update: count_new must be finite and >= rows");
+  if (!isfinite(std_min) || !isfinite(std_max) || !(std_min > 0.0f) || !(std_min <= std_max))
+    return lerr(PP3_ERR_ARG, "pp3_learner_normalizer_update: std_min and std_max must be finite, 0 < std_min <= std_max");
   LHIP(hipSetDevice(L->device));
   hipStream_t st = (hipStream_t)stream;
-  const int K = nsteps, B = batch, R = K * B, RV = (K + 1) * B;
-  const NetShape &ps = L->net[0], &vsn = L->net[1];
-  const size_t nx = (size_t)RV * ps.in_dim;
-  hipLaunchKernelGGL(gather_obs_kernel, dim3((unsigned)((nx + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0, st, obs_all,
-                     mean, std_dev, RV, B, num_envs, e0, ps.in_dim, L->x0);
-  RowArgs a{};
-  a.reward = reward; a.done = done; a.trunc = truncation; a.old_logp = log_prob; a.raw = raw_action; a.eps = eps;
-  a.vs = L->vs; a.adv = L->adv; a.row_a = L->row_a; a.row_b = L->row_b; a.stats = L->stats; a.metrics = metrics_dev;
-  a.K = K; a.B = B; a.N = num_envs; a.e0 = e0;
-  a.discount = discount; a.lambda = gae_lambda; a.reward_scaling = reward_scaling; a.clip_eps = clip_eps;
-  a.entropy_cost = entropy_cost; a.min_std = L->min_std; a.var_scale = L->var_scale;
-  a.normalize = normalize_advantage ? 1 : 0;
-  // the critic: baseline and bootstrap rows, targets, its gradient
-  a.values = forward(L, vsn, L->blob[1][0], RV, st);
-  a.dvalue = L->d[1];  // [R][1]: the value net's last delta
-  hipLaunchKernelGGL(value_head_kernel, dim3((B + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, st, a);
-  hipLaunchKernelGGL(value_stats_kernel, dim3(1), dim3(RED_BLOCK), 0, st, a);
-  // (backward writes its deltas to d[0], d[1], d[0], ..: each product reads one buffer and writes the other)
-  backward(L, vsn, L->blob[1][0], L->blob[1][1], a.dvalue, RV, R, st);
-  // the actor
-  a.logits = forward(L, ps, L->blob[0][0], R, st);
-  a.dlogits = L->d[1];
-  hipLaunchKernelGGL(policy_head_kernel, dim3((R + NTHREAD - 1) / NTHREAD), dim3(NTHREAD), 0, st, a);
-  hipLaunchKernelGGL(metrics_kernel, dim3(1), dim3(RED_BLOCK), 0, st, a);
-  backward(L, ps, L->blob[0][0], L->blob[0][1], a.dlogits, R, R, st);
+  const int in_dim = L->net[0].in_dim;
+  const int64_t rpr = (rows + NORM_RANGES - 1) / NORM_RANGES;
+  const int nr = (int)((rows + rpr - 1) / rpr);  // the non-empty ranges, <= NORM_RANGES
+  hipLaunchKernelGGL(norm_sweep_kernel<0>, dim3(nr), dim3(NTHREAD), 0, st, obs, rows, rpr, in_dim, mean, L->norm_mean,
+                     L->norm_part);
+  hipLaunchKernelGGL(norm_finish_kernel<0>, dim3(1), dim3(RED_BLOCK), 0, st, L->norm_part, nr, in_dim, count_new,
+                     std_min, std_max, mean, L->norm_mean, summed_variance, std_dev);
+  hipLaunchKernelGGL(norm_sweep_kernel<1>, dim3(nr), dim3(NTHREAD), 0, st, obs, rows, rpr, in_dim, mean, L->norm_mean,
+                     L->norm_part);
+  hipLaunchKernelGGL(norm_finish_kernel<1>, dim3(1), dim3(RED_BLOCK), 0, st, L->norm_part, nr, in_dim, count_new,
+                     std_min, std_max, mean, L->norm_mean, summed_variance, std_dev);
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_grad_clip(pp3_learner_t* L, float max_norm, float* norm_dev, void* stream) {
+  if (!L) return lerr(PP3_ERR_ARG, "pp3_grad_clip: null learner");
+  if (!isfinite(max_norm) || !(max_norm > 0.0f)) return lerr(PP3_ERR_ARG, "pp3_grad_clip: max_norm must be finite and > 0");
+  LHIP(hipSetDevice(L->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n0 = (int64_t)L->net[0].count, n = n0 + (int64_t)L->net[1].count;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(L->clip_blocks), dim3(NTHREAD), 0, st, L->blob[0][1], n0, L->blob[1][1], n,
+                     L->clip_part);
+  hipLaunchKernelGGL(grad_clip_kernel, dim3(L->clip_blocks), dim3(NTHREAD), 0, st, L->blob[0][1], n0, L->blob[1][1], n,
+                     L->clip_part, L->clip_blocks, max_norm, norm_dev);
   LHIP(hipGetLastError());
   return PP3_OK;
 }

@@ -7,9 +7,14 @@ handles from the trained parameters, all on the env's stream without a host roun
     actor, critic = learner.make_policies()
     state, metrics, key = learner.train_iteration(env, state, key, actor, critic, nsteps=20)
 
-Not here (follow-ups): the running-statistics update of the normaliser, shuffled minibatches (an
-index gather; minibatches are contiguous env ranges), gradient clipping and learning-rate
-schedules, bf16 / mixed precision, the multi-GPU gradient all-reduce.
+Off by default, the rest of Brax's training_step: the running observation normaliser
+(`running_statistics=True`, `update_normalizer`), a fresh env permutation per update pass
+(`set_env_index`, `loss_and_grad(indexed=True)`; `rng.permutation`) and optax's global-norm clip
+(`clip_gradients`); `train_iteration(shuffle=, max_grad_norm=, update_normalizer=)` chains them in
+Brax's order.
+
+Not here (follow-ups): learning-rate schedules (`lr` is a per-call argument), bf16 / mixed
+precision, the multi-GPU all-reduce of gradients and statistics.
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ from . import _abi, _lib, rng
 from .export import DevicePolicy, layers_blob
 
 ROW_CHUNK = 256  # PP3_LEARN_ROW_CHUNK: rows per partial sum of the weight gradient
+NORM_RANGES = 1024  # row ranges of the normaliser update's first level: ceil(rows / NORM_RANGES) rows each
 METRICS = ("total_loss", "policy_loss", "v_loss", "entropy_loss")
 HPARAMS = dict(discount=0.97, gae_lambda=0.95, reward_scaling=1.0, clipping_epsilon=0.3, entropy_cost=1e-2,
                normalize_advantage=True)
@@ -40,10 +46,14 @@ class PPOLearner:
     """Trainable copies of a policy (`export.convert_training_params`) and a value network
     (`export.convert_value_params`) whose layers were converted UN-folded (a normaliser of mean 0
     and std 1), plus the normaliser itself (`normalizer` = (mean, std) or an object with .mean and
-    .std; None: identity), held on the device with their gradients and Adam moments."""
+    .std; None: identity), held on the device with their gradients and Adam moments.
+    `running_statistics`: the normaliser is Brax's running_statistics state (mean, std,
+    summed_variance on the device, the count a Python int) that `update_normalizer` advances;
+    `normalizer` may then also carry .summed_variance and .count, and None starts from Brax's
+    initial state (count 0, mean 0, summed_variance 0, std 1)."""
 
     def __init__(self, policy_dict: Dict[str, Any], value_dict: Dict[str, Any], normalizer=None, device: int = 0,
-                 max_rows: int = 21 * 4096):
+                 max_rows: int = 21 * 4096, running_statistics: bool = False):
         L = _lib.load()
         self._L = L
         dist = policy_dict.get("distribution")
@@ -64,16 +74,27 @@ class PPOLearner:
         if rc != 0:
             raise _lib.PupperHipError(L.pp3_learn_last_error().decode())
         self._h = h
-        self._norm = None
-        if normalizer is not None:
-            mean, std = (normalizer if isinstance(normalizer, (tuple, list))
-                         else (normalizer.mean, normalizer.std))
-            ms = np.ascontiguousarray(np.stack([np.asarray(mean, np.float32), np.asarray(std, np.float32)]))
-            if ms.shape != (2, pin):
+        self._norm = None  # rows: mean, std, summed_variance
+        self.running_statistics = bool(running_statistics)
+        self._count = 0    # the normaliser's count (running_statistics)
+        if normalizer is not None or self.running_statistics:
+            sv = np.zeros(pin, np.float32)
+            if normalizer is None:
+                mean, std = np.zeros(pin, np.float32), np.ones(pin, np.float32)
+            elif isinstance(normalizer, (tuple, list)):
+                mean, std = normalizer
+            else:
+                mean, std = normalizer.mean, normalizer.std
+                sv = getattr(normalizer, "summed_variance", sv)
+                self._count = int(getattr(normalizer, "count", 0))
+            rows = [np.asarray(a, np.float32) for a in (mean, std, sv)]
+            if any(a.shape != (pin,) for a in rows):
                 raise ValueError(f"the normaliser needs mean and std of {pin} entries")
+            ms = np.ascontiguousarray(np.stack(rows))
             self._norm = _lib.DeviceBuffer(ms.nbytes, self.device)
             self._norm.upload(ms)
         self._metrics = _lib.DeviceBuffer(16, self.device)
+        self._gnorm = _lib.DeviceBuffer(4, self.device)  # the last clip_gradients' norm
         self._eps = None  # (key bytes, shape, DeviceBuffer)
         self._env = None  # the env whose stream the last call ran on
         self.t = 0        # Adam steps taken
@@ -89,6 +110,12 @@ class PPOLearner:
         if self._norm is None:
             return None, None
         return C.c_void_p(self._norm.ptr.value), C.c_void_p(self._norm.ptr.value + 4 * self.in_dim)
+
+    def _stream(self, stream=None):
+        """`stream`, by default the stream of the env the last call ran on (else the default stream)."""
+        if stream is None and self._env is not None:
+            stream = self._env._L.pp3_stream(self._env._h)
+        return C.c_void_p(stream) if stream else None
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -133,11 +160,14 @@ class PPOLearner:
     def loss_and_grad_device(self, K: int, B: int, N: int, e0: int, obs_all: int, raw_action: int, log_prob: int,
                              reward: int, done: int, truncation: int, eps: int, stream=None, discount: float = 0.97,
                              gae_lambda: float = 0.95, reward_scaling: float = 1.0, clipping_epsilon: float = 0.3,
-                             entropy_cost: float = 1e-2, normalize_advantage: bool = True) -> None:
-        """pp3_ppo_loss_grad on device addresses (arrays of a batch of N envs and K steps, see the header)."""
+                             entropy_cost: float = 1e-2, normalize_advantage: bool = True,
+                             indexed: bool = False) -> None:
+        """pp3_ppo_loss_grad on device addresses (arrays of a batch of N envs and K steps, see the header);
+        indexed: pp3_ppo_loss_grad_indexed, rows [e0, e0 + B) of the index of set_env_index."""
         p = lambda v: C.c_void_p(v) if v else None
         mean, std = self._norm_ptrs()
-        self._check(self._L.pp3_ppo_loss_grad(
+        fn = self._L.pp3_ppo_loss_grad_indexed if indexed else self._L.pp3_ppo_loss_grad
+        self._check(fn(
             self._h, int(K), int(B), int(N), int(e0), p(obs_all), p(raw_action), p(log_prob), p(reward), p(done),
             p(truncation), p(eps), mean, std, float(discount), float(gae_lambda), float(reward_scaling),
             float(clipping_epsilon), float(entropy_cost), int(bool(normalize_advantage)), self._metrics.ptr,
@@ -157,9 +187,10 @@ class PPOLearner:
             self._eps = (tag, buf)
         return self._eps[1].ptr.value
 
-    def loss_and_grad(self, env, e0: int, B: int, eps_key, **hparams) -> None:
-        """Loss and gradients on envs [e0, e0 + B) of the env's last collect_ppo batch, on the env's
-        stream.  hparams: HPARAMS' keys.  Results: grads(), metrics()."""
+    def loss_and_grad(self, env, e0: int, B: int, eps_key, indexed: bool = False, **hparams) -> None:
+        """Loss and gradients on envs [e0, e0 + B) of the env's last collect_ppo batch (indexed: on
+        the envs index[e0 : e0 + B] of set_env_index), on the env's stream.  hparams: HPARAMS' keys.
+        Results: grads(), metrics()."""
         dev = env.ppo_device_batch()
         ptr, (K, N, D) = dev["observation"]
         if D != self.in_dim:
@@ -169,7 +200,50 @@ class PPOLearner:
         self._env = env
         self.loss_and_grad_device(K, B, N, e0, ptr, dev["raw_action"][0], dev["log_prob"][0], dev["reward"][0],
                                   dev["done"][0], dev["truncation"][0], eps, env._L.pp3_stream(env._h),
-                                  **{**HPARAMS, **hparams})
+                                  **{**HPARAMS, **hparams}, indexed=indexed)
+
+    def set_env_index(self, index, stream=None) -> None:
+        """The env index behind loss_and_grad(indexed=True): int32 [num_envs], every entry in
+        [0, num_envs) (checked on the host; e.g. rng.permutation).  Copied in stream order."""
+        idx = np.ascontiguousarray(np.asarray(index, dtype=np.int32).ravel())
+        self._check(self._L.pp3_learner_set_env_index(self._h, _vp(idx), idx.size, self._stream(stream)))
+
+    def update_normalizer(self, env, std_min: float = 1e-6, std_max: float = 1e6) -> None:
+        """Brax's running_statistics.update with the observations the actor saw in the env's last
+        collect_ppo batch ([K][N][36H]; the bootstrap row is not read), on the env's stream."""
+        if not self.running_statistics:
+            raise ValueError("update_normalizer needs PPOLearner(running_statistics=True)")
+        ptr, (K, N, D) = env.ppo_device_batch()["observation"]
+        if D != self.in_dim:
+            raise ValueError(f"the batch's observations have {D} entries, the networks read {self.in_dim}")
+        self._env = _base(env)
+        count = self._count + K * N
+        base = self._norm.ptr.value
+        self._check(self._L.pp3_learner_normalizer_update(
+            self._h, C.c_void_p(ptr), K * N, float(np.float32(count)), float(std_min), float(std_max), C.c_void_p(base),
+            C.c_void_p(base + 8 * self.in_dim), C.c_void_p(base + 4 * self.in_dim), self._stream()))
+        self._count = count
+
+    def normalizer_state(self) -> Dict[str, Any]:
+        """dict(mean, std, summed_variance, count) downloaded (export, checkpoints); waits for the stream."""
+        if self._norm is None:
+            raise ValueError("this learner has no normaliser")
+        self._wait()
+        ms = np.empty((3, self.in_dim), np.float32)
+        self._norm.download(ms)
+        return dict(mean=ms[0], std=ms[1], summed_variance=ms[2], count=self._count)
+
+    def clip_gradients(self, max_norm: float, stream=None) -> None:
+        """optax.clip_by_global_norm on the gradients of the last loss_and_grad (pp3_grad_clip),
+        before adam_step; the norm: grad_norm()."""
+        self._check(self._L.pp3_grad_clip(self._h, float(max_norm), self._gnorm.ptr, self._stream(stream)))
+
+    def grad_norm(self) -> float:
+        """The global gradient norm the last clip_gradients measured (before clipping; waits for it)."""
+        self._wait()
+        out = np.empty(1, np.float32)
+        self._gnorm.download(out)
+        return float(out[0])
 
     def adam_step(self, lr: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8, stream=None) -> None:
         """optax.adam's update of both nets from the gradients of the last loss_and_grad.  stream: by
@@ -202,11 +276,17 @@ class PPOLearner:
                                                        _vp(outs), mean, std, C.c_void_p(stream) if stream else None))
 
     def train_iteration(self, env, state, key, device_policy: DevicePolicy, device_value: DevicePolicy, nsteps: int,
-                        num_minibatches: int = 1, num_updates_per_batch: int = 1, lr: float = 3e-4, **hparams):
-        """One PPO iteration: collect_ppo with the handles, num_updates_per_batch passes over
-        num_minibatches contiguous env ranges (loss, gradient, Adam each), then the reload.
-        key -> (collect key, entropy-noise key) by rng.split.  Returns (state, metrics of the last
-        minibatch, the collect's key chain end)."""
+                        num_minibatches: int = 1, num_updates_per_batch: int = 1, lr: float = 3e-4,
+                        shuffle: bool = False, max_grad_norm: Optional[float] = None, update_normalizer: bool = False,
+                        **hparams):
+        """One PPO iteration in Brax's training_step order: collect_ppo with the handles (the old
+        parameters and statistics), update_normalizer: the running statistics, then
+        num_updates_per_batch passes over num_minibatches minibatches (loss, gradient, max_grad_norm:
+        the clip, Adam each) with the new statistics, then the reload.  Minibatches are contiguous
+        env ranges, or with shuffle ranges [mb B, (mb + 1) B) of a fresh rng.permutation per pass.
+        key -> (collect key, entropy-noise key) by rng.split; with shuffle k_perm = split(entropy-
+        noise key)[1] and per pass k_perm, k_u = split(k_perm), the pass's index from k_u.  Returns
+        (state, metrics of the last minibatch, the collect's key chain end)."""
         base = _base(env)
         n = base.num_envs
         if n % num_minibatches:
@@ -215,9 +295,18 @@ class PPOLearner:
         k_collect, k_eps = rng.split(np.asarray(key, dtype=np.uint32).reshape(2), 2, base._partitionable)
         gae = {k: hparams[k] for k in ("discount", "gae_lambda", "reward_scaling") if k in hparams}
         state, _, k_out = env.collect_ppo(state, device_policy, device_value, nsteps, k_collect, **gae)
+        if update_normalizer:
+            self.update_normalizer(env)
+        k_perm = rng.split(k_eps, 2, base._partitionable)[1] if shuffle else None
         for _ in range(num_updates_per_batch):
+            if shuffle:
+                k_perm, k_u = rng.split(k_perm, 2, base._partitionable)
+                self._env = base
+                self.set_env_index(rng.permutation(k_u, n, base._partitionable))
             for mb in range(num_minibatches):
-                self.loss_and_grad(env, mb * B, B, k_eps, **hparams)
+                self.loss_and_grad(env, mb * B, B, k_eps, indexed=bool(shuffle), **hparams)
+                if max_grad_norm is not None:
+                    self.clip_gradients(max_grad_norm)
                 self.adam_step(lr)
         self.sync(device_policy, device_value)
         return state, self.metrics(), k_out
@@ -226,7 +315,7 @@ class PPOLearner:
         if getattr(self, "_h", None):
             self._L.pp3_learner_destroy(self._h)
             self._h = None
-            for b in (self._norm, self._metrics, self._eps[1] if self._eps else None):
+            for b in (self._norm, self._metrics, self._gnorm, self._eps[1] if self._eps else None):
                 if b is not None:
                     b.free()
 

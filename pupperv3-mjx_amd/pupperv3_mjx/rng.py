@@ -15,7 +15,9 @@ requirements.txt:2): ``split`` (environment.py:315,349,506; domain_randomization
 * ``uniform``: bits >> 9 | 0x3f800000 reinterpreted as f32, minus 1, scaled, max(minval, .);
   ``bernoulli(p)`` = uniform < p; ``choice(p)`` = searchsorted_left(cumsum(p), cumsum[-1]*(1-u));
 * ``normal`` (the PPO actor's noise, not drawn by the env itself): sqrt(2) * erfinv of the
-  uniform on (-1, 1) -- the uniform bit for bit, erfinv to f32 rounding (see ``normal``).
+  uniform on (-1, 1) -- the uniform bit for bit, erfinv to f32 rounding (see ``normal``);
+* ``permutation(key, n)`` (Brax PPO's minibatch shuffle): jax's ``_shuffle`` on ``arange(n)``,
+  rounds of split / 32 random bits / stable sort.
 
 All float arithmetic here is float32 to match JAX with x64 disabled.
 """
@@ -124,6 +126,23 @@ def normal(key, shape, partitionable: bool = True) -> np.ndarray:
     lo = np.nextafter(np.float32(-1.0), np.float32(0.0))
     u = uniform(key, shape, lo, 1.0, partitionable)
     return (np.sqrt(2.0) * erfinv(u.astype(np.float64))).astype(np.float32)
+
+
+def permutation(key, n: int, partitionable: bool = True) -> np.ndarray:
+    """jax.random.permutation(key, n) restated (jax's _shuffle on arange(n)): ceil(3 ln(max(1, n)) /
+    ln(2^32 - 1)) rounds, each one `key, sub = split(key)`, 32 random bits per element from `sub`,
+    and a stable sort of the current array by those bits.  -> int32 [n].  (Brax PPO's sgd_step
+    permutes the env axis with it once per update pass.)"""
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    x = np.arange(n, dtype=np.int32)
+    rounds = int(np.ceil(3.0 * np.log(max(1, n)) / np.log(2.0 ** 32 - 1.0)))
+    key = np.asarray(key, dtype=np.uint32).reshape(2)
+    for _ in range(rounds):
+        key, sub = split(key, 2, partitionable)
+        x = x[np.argsort(random_bits32(sub, n, partitionable), kind="stable")]
+    return x
 
 
 def bernoulli(key, p: float, shape=(), partitionable: bool = True) -> np.ndarray:

@@ -6,7 +6,13 @@ between device events, medians over `--repeat` alternating rounds with the run-t
   (b) the reload of both handles (pp3_policy_load_params);
   (c) reference 1: the sampled rollout of the same run (pp3_rollout_policy_sample_timed, K steps);
   (d) reference 2, the yardstick for time: the same loss and gradient by torch eager autograd in
-      f32 on the same device and rows (tests/ppo_loss_ref.py `loss`, no optimiser step).
+      f32 on the same device and rows (tests/ppo_loss_ref.py `loss`, no optimiser step);
+  (e) the rest of training_step: pp3_learner_normalizer_update over the batch's K * envs rows (with the
+      GB/s of its two sweeps) beside the same update in torch eager f32 on the same rows; pp3_grad_clip
+      below the bound (norm only) and above it (norm and scaling); (a) through
+      pp3_ppo_loss_grad_indexed on a permutation of the envs.  Skipped on a library without them.
+"plain_grad_crc32" / "rollout_crc32" (the first plain loss's gradients and metrics; an untimed
+rollout's outputs) compare the plain path's result bits between two builds (PP3_LIB_PATH).
 One child process under a time limit.
 
   python tools/ppo_learn_bench.py [--envs 4096 --warmup 200 --steps 20 --minibatch 256 --repeat 9 --timeout 300]
@@ -25,6 +31,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "pupperv3-mjx_amd"), os.path.join(ROOT,
 def child(E: int, W: int, K: int, MB: int, R: int) -> None:
     from collections import OrderedDict
     from types import SimpleNamespace
+
+    import zlib
 
     import numpy as np
     import torch
@@ -73,9 +81,15 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
         assert raw_lib.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
         return ms.value
 
-    def step(B):
-        learner.loss_and_grad(env, 0, B, k_eps)
+    def step(B, indexed=False):
+        learner.loss_and_grad(env, 0, B, k_eps, indexed=indexed)
         learner.adam_step(3e-4)
+
+    def crc(*arrays):
+        c = 0
+        for a in arrays:
+            c = zlib.crc32(np.ascontiguousarray(a).tobytes(), c)
+        return c
 
     # the same rows for torch: its own copies on the same device
     dev = torch.device("cuda:0")
@@ -101,6 +115,7 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
     # parity of what is timed: the two compute the same loss
     learner.loss_and_grad(env, 0, MB, k_eps)
     ours = learner.metrics()["total_loss"]
+    plain_crc = crc(np.array(list(learner.metrics().values()), np.float32), learner._download(0, 1), learner._download(1, 1))
     _, theirs, _ = torch_step(MB)
     act, raw = _lib.DeviceBuffer(4 * K * E * 12), _lib.DeviceBuffer(4 * K * E * 12)
     logp, rew, done = (_lib.DeviceBuffer(4 * K * E) for _ in range(3))
@@ -113,12 +128,72 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
                                                      done.ptr, obs.ptr, C.byref(ms)))
         return ms.value
 
+    rollout()
+    got_bufs = []
+    for buf, count in ((act, K * E * 12), (raw, K * E * 12), (logp, K * E), (rew, K * E), (done, K * E), (obs, K * E * D)):
+        a = np.empty(count, np.float32)
+        buf.download(a)
+        got_bufs.append(a)
+    rollout_crc = crc(*got_bufs)
+
+    # the rest of training_step (a library with the entry points): the normaliser on a state of its
+    # own, the clip on the gradients the step before it left, the indexed loss on a permutation
+    extra = hasattr(raw_lib, "pp3_grad_clip")
+    rows = K * E
+    obs_ptr = env.ppo_device_batch()["observation"][0]
+    nstate = _lib.DeviceBuffer(12 * D)
+    nstate.upload(np.stack([np.zeros(D), np.zeros(D), np.ones(D)]).astype(np.float32))
+    ncount = [0]
+
+    def norm_update():
+        ncount[0] += rows
+        b = nstate.ptr.value
+        rc = raw_lib.pp3_learner_normalizer_update(learner._h, C.c_void_p(obs_ptr), rows, float(np.float32(ncount[0])), 1e-6,
+                                                   1e6, C.c_void_p(b), C.c_void_p(b + 4 * D), C.c_void_p(b + 8 * D), stream)
+        assert rc == 0, raw_lib.pp3_learn_last_error()
+
+    tx = tb[E]["obs_all"][:K].reshape(rows, D)
+    tstate = [torch.zeros(D, device=dev), torch.zeros(D, device=dev), 0]
+
+    def torch_norm():
+        tev[0].record()
+        mean, sv, count = tstate
+        count += rows
+        d = tx - mean
+        mean2 = mean + d.sum(0) / count
+        sv2 = sv + (d * (tx - mean2)).sum(0)
+        std = torch.clamp(torch.sqrt(torch.clamp(sv2, min=0) / count), 1e-6, 1e6)
+        tev[1].record()
+        tev[1].synchronize()
+        tstate[:] = [mean2, sv2, count]
+        return tev[0].elapsed_time(tev[1]), mean2, std
+
+    norm_check = None
+    if extra:
+        timed(norm_update)
+        first = np.empty((3, D), np.float32)
+        nstate.download(first)
+        _, tmean, tstd = torch_norm()
+        norm_check = {"mean": float(np.abs(first[0] - tmean.cpu().numpy()).max() / np.abs(first[0]).max()),
+                      "std": float(np.abs(first[2] - tstd.cpu().numpy()).max() / np.abs(first[2]).max())}
+        learner._env = env
+        learner.set_env_index(rng.permutation(rng.PRNGKey(3), E))
+
     names = ("learn_minibatch_ms", "learn_batch_ms", "reload_ms", "rollout_ms", "torch_minibatch_ms", "torch_batch_ms")
+    if extra:
+        names += ("norm_update_ms", "torch_norm_ms", "clip_norm_only_ms", "clip_scale_ms", "learn_minibatch_indexed_ms",
+                  "learn_batch_indexed_ms")
     out = {k: [] for k in names}
     for r in range(R + 2):  # rounds 0 and 1 warm every shape up
         got = dict(learn_minibatch_ms=timed(lambda: step(MB)), torch_minibatch_ms=torch_step(MB)[0],
                    learn_batch_ms=timed(lambda: step(E)), torch_batch_ms=torch_step(E)[0],
                    reload_ms=timed(lambda: learner.sync(actor, critic)), rollout_ms=rollout())
+        if extra:
+            got.update(norm_update_ms=timed(norm_update), torch_norm_ms=torch_norm()[0],
+                       learn_minibatch_indexed_ms=timed(lambda: step(MB, True)),
+                       learn_batch_indexed_ms=timed(lambda: step(E, True)),
+                       clip_norm_only_ms=timed(lambda: learner.clip_gradients(1e30)),
+                       clip_scale_ms=timed(lambda: learner.clip_gradients(1e-3)))
         if r >= 2:
             for k, v in got.items():
                 out[k].append(round(v, 4))
@@ -130,8 +205,17 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
                       "learn_over_torch": {"minibatch": round(med["learn_minibatch_ms"] / med["torch_minibatch_ms"], 3),
                                            "batch": round(med["learn_batch_ms"] / med["torch_batch_ms"], 3)},
                       "learn_batch_share_of_rollout": round(med["learn_batch_ms"] / med["rollout_ms"], 3),
+                      **({"norm_update_gb_per_s": round(2 * rows * D * 4 / (med["norm_update_ms"] * 1e6), 1),
+                          "norm_update_over_torch": round(med["norm_update_ms"] / med["torch_norm_ms"], 3),
+                          "share_of_rollout": {k: round(med[k] / med["rollout_ms"], 4)
+                                               for k in ("norm_update_ms", "clip_scale_ms", "learn_batch_indexed_ms")},
+                          "indexed_over_plain": {"minibatch": round(med["learn_minibatch_indexed_ms"] / med["learn_minibatch_ms"], 3),
+                                                 "batch": round(med["learn_batch_indexed_ms"] / med["learn_batch_ms"], 3)},
+                          "norm_first_update_vs_torch": norm_check} if extra else {}),
+                      "plain_grad_crc32": plain_crc, "rollout_crc32": rollout_crc,
                       "first_total_loss": {"learner": ours, "torch": theirs},
                       "losses_finite": bool(all(np.isfinite(v) for v in final.values()))}), flush=True)
+    nstate.free()
     for e in ev:
         raw_lib.hipEventDestroy(e)
     actor.close()
