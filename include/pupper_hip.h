@@ -716,6 +716,58 @@ int pp3_ppo_loss_grad_indexed(pp3_learner_t* learner, int32_t nsteps, int32_t ba
  *   norm < max_norm: the gradients stay bit for bit as they were;  else g <- (g / norm) * max_norm.
  * PP3_ERR_ARG: a null learner, max_norm not finite or <= 0. */
 int pp3_grad_clip(pp3_learner_t* learner, float max_norm, float* norm_dev, void* stream);
+
+/* ---- PPO learner across ranks: rank-ordered gradient and statistics reduce (additive; ABI stays 2) ----
+ * Data-parallel PPO over a communicator handle, pp3_comm_t: what [ext] brax 0.12.1 training_step does
+ * under pmap, restated from memory; what is written here is the contract.  Every rank holds a replica
+ * of the learner, collects and differentiates on its own env shard, and the replicas stay bit-identical
+ * because every cross-rank sum has ONE order.  ncclAllReduce promises no order of additions, so it is
+ * not used: each rank all-gathers the ranks' contributions ([world][count], rank r's at row r) and a
+ * kernel adds them in rank order, starting from rank 0's value, in f32, each addition rounded on its
+ * own.  Every rank computes the same bits from the same gathered data, whatever the transport.  The
+ * ranks must start from identical parameters, moments and statistics; each passes its own PRNG key.
+ * Errors are PP3_ERR_ARG through pp3_learn_last_error before any launch or collective, outputs
+ * untouched: a null pointer, a world size outside 1 .. PP3_LEARN_MAX_WORLD, a communicator on another
+ * device than the learner's (and the per-call conditions below).  A failing collective returns
+ * PP3_ERR_COMM.  All calls are enqueued on `stream` with no host synchronisation; the workspaces
+ * belong to the learner and are allocated at the first call for a given world size.
+ *
+ * 1. Gradients and metrics (jax.lax.pmean of both).  After a pp3_ppo_loss_grad* call, for every element
+ * i of "policy gradient blob, then value gradient blob, then the 4 metrics" (count = policy count +
+ * value count + 4):
+ *   g[i] <- (((g_0[i] + g_1[i]) + g_2[i]) + ..) / (float)world, the quotient correctly rounded
+ * (world = 1: g[i] itself, bit for bit).  The mean is unweighted, as Brax's: with shards of unequal
+ * size a rank's rows weigh 1 / (world * its row count), which is the caller's business.  Advantage
+ * normalisation stays local to the rank's minibatch, as in Brax.  pp3_grad_clip and pp3_adam_step then
+ * run unchanged on the averaged gradient (optax's chain order).
+ * pp3_learner_allreduce_grads: ONE collective per minibatch: a kernel packs the three pieces into one
+ * contiguous send of `count` floats, one all-gather, then the reduce kernel; it reads and rewrites
+ * the learner's gradient blobs and metrics_dev f32[4].  No shortcut at world = 1.
+ * pp3_learner_reduce_gathered: the reduce kernel on its own, from gathered_dev [world][count] on the
+ * learner's device into both gradient blobs and metrics_dev (one launch, no collective): what
+ * pp3_learner_allreduce_grads runs after its gather, for tests and measurements at any world size.
+ *
+ * 2. Running statistics (running_statistics.update with pmap_axis_name: its two psums).
+ * pp3_learner_normalizer_update_ranks is pp3_learner_normalizer_update (same arguments, and its errors)
+ * with obs [rows][in_dim] this rank's own rows and count_new = the old count + the sum over ranks of
+ * their rows (the caller's; finite and >= rows).  Per column k, the rank sums starting from rank 0's
+ * term:
+ *   S_r      = sum over rank r's rows of (obs[.][k] - mean[k])
+ *   mean'[k] = mean[k] + ((S_0 / count_new + S_1 / count_new) + ..)     each quotient correctly rounded
+ *   V_r      = sum over rank r's rows of (obs[.][k] - mean[k]) * (obs[.][k] - mean'[k])
+ *   sv'[k]   = sv[k] + ((V_0 + V_1) + ..)
+ *   std'[k]  = clip(sqrt(max(sv'[k], 0) / count_new), std_min, std_max)
+ * S_r and V_r are summed over the rank's own rows in the order pp3_learner_normalizer_update fixes for
+ * (rows, in_dim).  Each sweep is followed by an all-gather of in_dim floats (two collectives per
+ * update).  At world = 1 the result is pp3_learner_normalizer_update's bit for bit. */
+#define PP3_LEARN_MAX_WORLD 64
+typedef struct pp3_comm pp3_comm_t; /* the communicator of the Multi-GPU section below */
+int pp3_learner_allreduce_grads(pp3_learner_t* learner, pp3_comm_t* comm, float* metrics_dev, void* stream);
+int pp3_learner_reduce_gathered(pp3_learner_t* learner, const float* gathered_dev, int32_t world, float* metrics_dev,
+                                void* stream);
+int pp3_learner_normalizer_update_ranks(pp3_learner_t* learner, pp3_comm_t* comm, const float* obs, int64_t rows,
+                                        float count_new, float std_min, float std_max, float* mean,
+                                        float* summed_variance, float* std_dev, void* stream);
 const char* pp3_learn_last_error(void);
 
 /* ---------------------------------------------------------------------------------------
@@ -727,7 +779,7 @@ const char* pp3_learn_last_error(void);
  * obs | reward | done over RCCL (xGMI), launched on the env's stream behind the step kernel with
  * no host synchronisation.  RCCL is dlopen'ed on first use (the single-GPU path never loads it).
  * ------------------------------------------------------------------------------------- */
-typedef struct pp3_comm pp3_comm_t;
+/* the handle type pp3_comm_t is declared above pp3_learner_allreduce_grads */
 #define PP3_COMM_ID_BYTES 128 /* ncclUniqueId */
 enum { PP3_REDUCE_SUM = 0, PP3_REDUCE_MAX = 1 };
 /* Rank 0 creates the communicator id and hands its 128 bytes to the other ranks out of band. */
@@ -755,6 +807,14 @@ int pp3_gather(pp3_comm_t* comm, pp3_env_t* env, int32_t nmax, int32_t root, flo
 int pp3_gather_rollout(pp3_comm_t* comm, pp3_env_t* env, const float* traj_obs, const float* traj_reward,
                        const float* traj_done, int32_t nsteps, int32_t nmax, int32_t root, float* dst_dev,
                        void* stream);
+/* A plain device all-gather of f32: rank r's `count` floats at send_dev land at recv_dev + r * count on
+ * every rank (recv_dev holds world * count floats; both on the communicator's device).  Enqueued on
+ * `stream` (NULL = the default stream) with no host synchronisation; the caller's current HIP device
+ * is restored on return.  PP3_ERR_ARG (no collective): a null pointer, count < 1.  The learner's
+ * rank-ordered reduces are built on it. */
+int pp3_comm_allgather_f32(pp3_comm_t* comm, const float* send_dev, float* recv_dev, int64_t count, void* stream);
+/* The device the communicator was created on (-1 for NULL). */
+int32_t pp3_comm_device(const pp3_comm_t* comm);
 /* Host-blocking helpers for timing: element-wise sum / max of n <= 64 doubles over ranks, and
  * a barrier. */
 int pp3_comm_allreduce(pp3_comm_t* comm, const double* in, double* out, int32_t n, int32_t op);

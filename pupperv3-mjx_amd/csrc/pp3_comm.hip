@@ -307,6 +307,19 @@ int pp3_gather_rollout(pp3_comm_t* c, pp3_env_t* e, const float* traj_obs, const
   return exchange(c, R, mine, count, root, dst_dev, s);
 }
 
+int32_t pp3_comm_device(const pp3_comm_t* c) { return c ? c->device : -1; }
+
+int pp3_comm_allgather_f32(pp3_comm_t* c, const float* send_dev, float* recv_dev, int64_t count, void* stream) {
+  if (!c || !send_dev || !recv_dev) return cerr(PP3_ERR_ARG, "pp3_comm_allgather_f32: null argument");
+  if (count < 1) return cerr(PP3_ERR_ARG, "pp3_comm_allgather_f32: count must be >= 1");
+  const Rccl* R = rccl();
+  if (!R) return cerr(PP3_ERR_COMM, g_cerr);
+  DeviceScope dev(c->device);
+  HCHK(dev.err);
+  NCHK(R, R->AllGather(send_dev, recv_dev, (size_t)count, ncclFloat32, c->comm, (hipStream_t)stream));
+  return PP3_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -21,6 +21,12 @@
 // column, per-row-range partials, a single-block finish), shuffled minibatches (a validated env index
 // the three batch-reading kernels read through; NULL is the contiguous range) and the global-norm
 // gradient clip (pp3_grad_clip), all with the same fixed-order sums.
+//
+// Across ranks (data-parallel PPO over a pp3_comm_t): the gradient blobs and the metrics are packed
+// into one send, all-gathered, and added in rank order by one kernel (pp3_learner_allreduce_grads;
+// the kernel alone: pp3_learner_reduce_gathered); the normaliser's finish is cut in two around an
+// all-gather of one [in_dim] row per sweep (pp3_learner_normalizer_update_ranks).  No ncclAllReduce:
+// its order of additions is not fixed.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -387,12 +393,10 @@ __global__ __launch_bounds__(NTHREAD) void norm_sweep_kernel(const float* __rest
 // S[k] = sum over the nr ranges of part[range][k], then
 // PASS 0: mean_new[k] = mean[k] + S / count
 // PASS 1: sv[k] += S; std[k] = clip(sqrt(max(sv[k], 0) / count), std_min, std_max); mean[k] = mean_new[k]
-template <int PASS>
-__global__ __launch_bounds__(RED_BLOCK) void norm_finish_kernel(const float* __restrict__ part, int nr, int in_dim,
-                                                                float count, float std_min, float std_max,
-                                                                float* __restrict__ mean, float* __restrict__ mean_new,
-                                                                float* __restrict__ sv, float* __restrict__ stdv) {
-  __shared__ float sh[RED_BLOCK];
+// The range sum of the finishing workgroup (RED_BLOCK threads): the thread that ends up with column
+// k's sum S calls fin(k, S).
+template <class Fin>
+__device__ __forceinline__ void norm_range_sums(const float* __restrict__ part, int nr, int in_dim, float* sh, Fin fin) {
   const int tid = threadIdx.x;
   const int w = min(in_dim, NORM_FIN_COLS), G = RED_BLOCK / w;
   const int g = tid / w, kk = tid - g * w;
@@ -409,20 +413,91 @@ __global__ __launch_bounds__(RED_BLOCK) void norm_finish_kernel(const float* __r
     __syncthreads();
     if (g == 0 && k < in_dim) {
       for (int j = 1; j < G; j++) s += sh[j * w + kk];
-      if (PASS == 0) {
-        mean_new[k] = mean[k] + div_rn(s, count);
-      } else {
-        const float v = sv[k] + s;
-        sv[k] = v;
-        // (the build's fast sqrt is within 1 ulp; one residual step, as in div_rn)
-        const float q = div_rn(fmaxf(v, 0.0f), count);
-        float sd = sqrtf(q);
-        if (sd > 0.0f && sd < INFINITY) sd = fmaf(fmaf(-sd, sd, q), 0.5f / sd, sd);
-        stdv[k] = fminf(fmaxf(sd, std_min), std_max);
-        mean[k] = mean_new[k];
-      }
+      fin(k, s);
     }
   }
+}
+
+// What follows a column's sum: `t` is S / count (PASS 0) or S (PASS 1) on one GPU, and across ranks
+// the rank-ordered sum of the ranks' such terms.
+// PASS 0: mean_new[k] = mean[k] + t
+// PASS 1: sv[k] += t; std[k] = clip(sqrt(max(sv[k], 0) / count), std_min, std_max); mean[k] = mean_new[k]
+template <int PASS>
+__device__ __forceinline__ void norm_apply(int k, float t, float count, float std_min, float std_max,
+                                           float* __restrict__ mean, float* __restrict__ mean_new,
+                                           float* __restrict__ sv, float* __restrict__ stdv) {
+  if (PASS == 0) {
+    mean_new[k] = mean[k] + t;
+  } else {
+    const float v = sv[k] + t;
+    sv[k] = v;
+    // (the build's fast sqrt is within 1 ulp; one residual step, as in div_rn)
+    const float q = div_rn(fmaxf(v, 0.0f), count);
+    float sd = sqrtf(q);
+    if (sd > 0.0f && sd < INFINITY) sd = fmaf(fmaf(-sd, sd, q), 0.5f / sd, sd);
+    stdv[k] = fminf(fmaxf(sd, std_min), std_max);
+    mean[k] = mean_new[k];
+  }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(RED_BLOCK) void norm_finish_kernel(const float* __restrict__ part, int nr, int in_dim,
+                                                                float count, float std_min, float std_max,
+                                                                float* __restrict__ mean, float* __restrict__ mean_new,
+                                                                float* __restrict__ sv, float* __restrict__ stdv) {
+  __shared__ float sh[RED_BLOCK];
+  norm_range_sums(part, nr, in_dim, sh, [&](int k, float s) {
+    norm_apply<PASS>(k, PASS == 0 ? div_rn(s, count) : s, count, std_min, std_max, mean, mean_new, sv, stdv);
+  });
+}
+
+// ---- the same update across ranks: norm_finish_kernel cut in two around an all-gather ----
+// row[k] = S / count (PASS 0: count is the global count') or S (PASS 1), this rank's term
+template <int PASS>
+__global__ __launch_bounds__(RED_BLOCK) void norm_reduce_kernel(const float* __restrict__ part, int nr, int in_dim,
+                                                                float count, float* __restrict__ row) {
+  __shared__ float sh[RED_BLOCK];
+  norm_range_sums(part, nr, in_dim, sh, [&](int k, float s) { row[k] = PASS == 0 ? div_rn(s, count) : s; });
+}
+
+// t = ((rows[0][k] + rows[1][k]) + ..) over the ranks ascending, then norm_apply
+template <int PASS>
+__global__ __launch_bounds__(NTHREAD) void norm_apply_ranks_kernel(const float* __restrict__ rows, int world, int in_dim,
+                                                                   float count, float std_min, float std_max,
+                                                                   float* __restrict__ mean, float* __restrict__ mean_new,
+                                                                   float* __restrict__ sv, float* __restrict__ stdv) {
+  const int k = blockIdx.x * NTHREAD + threadIdx.x;
+  if (k >= in_dim) return;
+  float t = rows[k];
+  for (int r = 1; r < world; r++) t += rows[(size_t)r * in_dim + k];
+  norm_apply<PASS>(k, t, count, std_min, std_max, mean, mean_new, sv, stdv);
+}
+
+// ---- gradients and metrics across ranks (pmean): gather, then add in rank order ----
+// The gradient blobs and the 4 metrics as one array of n + 4 floats: element i is g0[i] for i < n0,
+// g1[i - n0] for i < n, else metrics[i - n].
+__global__ __launch_bounds__(NTHREAD) void pack_grads_kernel(const float* __restrict__ g0, int64_t n0,
+                                                             const float* __restrict__ g1, int64_t n,
+                                                             const float* __restrict__ metrics, float* __restrict__ send) {
+  const int64_t i = (int64_t)blockIdx.x * NTHREAD + threadIdx.x;
+  if (i >= n + 4) return;
+  send[i] = i < n0 ? g0[i] : (i < n ? g1[i - n0] : metrics[i - n]);
+}
+
+// element i <- (((gathered[0][i] + gathered[1][i]) + gathered[2][i]) + ..) / world, each addition
+// rounded on its own, the quotient correctly rounded; at world 1 the value itself
+__global__ __launch_bounds__(NTHREAD) void reduce_ranks_kernel(const float* __restrict__ gathered, int world, int64_t n0,
+                                                               int64_t n, float* __restrict__ g0, float* __restrict__ g1,
+                                                               float* __restrict__ metrics) {
+  const int64_t i = (int64_t)blockIdx.x * NTHREAD + threadIdx.x;
+  const int64_t total = n + 4;
+  if (i >= total) return;
+  float s = gathered[i];
+  for (int r = 1; r < world; r++) s += gathered[(size_t)r * (size_t)total + i];
+  if (world > 1) s = div_rn(s, (float)world);
+  if (i < n0) g0[i] = s;
+  else if (i < n) g1[i - n0] = s;
+  else metrics[i - n] = s;
 }
 
 // ---- the global-norm clip (optax.clip_by_global_norm) ----
@@ -549,6 +624,11 @@ struct pp3_learner {
   float* norm_mean;  // [in_dim] mean' between the two sweeps
   float* clip_part;  // [clip_blocks] the clip's partial sums of squares
   int clip_blocks;
+  // Across ranks (allocated at the first call for a world size): this rank's packed gradients and
+  // metrics [count + 4] followed by the gathered [world][count + 4]; likewise the normaliser's row.
+  float* rank_grads;
+  float* rank_norm;  // [1 + world][in_dim]
+  int rank_grads_world, rank_norm_world;
   // The env index: the device copy, and two pinned staging blocks taken in turn, each with the event
   // of the copy that last read it (pp3_learner_set_env_index waits for that one before refilling).
   int32_t* idx_dev;
@@ -793,7 +873,7 @@ int pp3_learner_destroy(pp3_learner_t* L) {
   for (int n = 0; n < 2; n++)
     for (int w = 0; w < 4; w++) (void)hipFree(L->blob[n][w]);
   float* ws[] = {L->x0, L->y, L->d[0], L->d[1], L->part, L->vs, L->adv, L->row_a, L->row_b, L->stats,
-                 L->norm_part, L->norm_mean, L->clip_part};
+                 L->norm_part, L->norm_mean, L->clip_part, L->rank_grads, L->rank_norm};
   for (float* p : ws) (void)hipFree(p);
   free_env_index(L);
   delete L;
@@ -887,6 +967,112 @@ int pp3_learner_normalizer_update(pp3_learner_t* L, const float* obs, int64_t ro
                      L->norm_part);
   hipLaunchKernelGGL(norm_finish_kernel<1>, dim3(1), dim3(RED_BLOCK), 0, st, L->norm_part, nr, in_dim, count_new,
                      std_min, std_max, mean, L->norm_mean, summed_variance, std_dev);
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+}  // extern "C"
+
+// [1 + world][count] floats at *buf, allocated at the first call for this world size (hipFree waits
+// for the queued work that reads the old one)
+static int rank_workspace(const char* fn, float** buf, int* have_world, int world, size_t count) {
+  if (*buf && *have_world == world) return PP3_OK;
+  (void)hipFree(*buf);
+  *buf = nullptr;
+  *have_world = 0;
+  if (hipMalloc(buf, (size_t)(1 + world) * count * sizeof(float)) != hipSuccess)
+    return lerr(PP3_ERR_NOMEM, std::string(fn) + ": device allocation failed");
+  *have_world = world;
+  return PP3_OK;
+}
+
+// the communicator's argument rules, shared by the two entry points that take one; sets *world
+static int check_comm(const std::string& f, pp3_learner* L, pp3_comm_t* comm, int* world) {
+  if (pp3_comm_device(comm) != L->device)
+    return lerr(PP3_ERR_ARG, f + ": the learner and the communicator are on different devices");
+  *world = pp3_comm_world(comm);
+  if (*world < 1 || *world > PP3_LEARN_MAX_WORLD)
+    return lerr(PP3_ERR_ARG, f + ": the communicator's world size must be in 1 .. 64");
+  return PP3_OK;
+}
+
+static void launch_reduce_ranks(pp3_learner* L, const float* gathered, int world, float* metrics_dev, hipStream_t st) {
+  const int64_t n0 = (int64_t)L->net[0].count, n = n0 + (int64_t)L->net[1].count;
+  hipLaunchKernelGGL(reduce_ranks_kernel, dim3((unsigned)((n + 4 + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0, st,
+                     gathered, world, n0, n, L->blob[0][1], L->blob[1][1], metrics_dev);
+}
+
+extern "C" {
+
+int pp3_learner_reduce_gathered(pp3_learner_t* L, const float* gathered_dev, int32_t world, float* metrics_dev,
+                                void* stream) {
+  if (!L || !gathered_dev || !metrics_dev) return lerr(PP3_ERR_ARG, "pp3_learner_reduce_gathered: null argument");
+  if (world < 1 || world > PP3_LEARN_MAX_WORLD)
+    return lerr(PP3_ERR_ARG, "pp3_learner_reduce_gathered: world must be in 1 .. 64");
+  LHIP(hipSetDevice(L->device));
+  launch_reduce_ranks(L, gathered_dev, world, metrics_dev, (hipStream_t)stream);
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_learner_allreduce_grads(pp3_learner_t* L, pp3_comm_t* comm, float* metrics_dev, void* stream) {
+  const std::string f = "pp3_learner_allreduce_grads";
+  if (!L || !comm || !metrics_dev) return lerr(PP3_ERR_ARG, f + ": null argument");
+  int world;
+  if (const int rc = check_comm(f, L, comm, &world)) return rc;
+  LHIP(hipSetDevice(L->device));
+  const int64_t n0 = (int64_t)L->net[0].count, n = n0 + (int64_t)L->net[1].count, total = n + 4;
+  if (const int rc = rank_workspace(f.c_str(), &L->rank_grads, &L->rank_grads_world, world, (size_t)total)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  float* send = L->rank_grads;
+  float* gathered = L->rank_grads + total;
+  hipLaunchKernelGGL(pack_grads_kernel, dim3((unsigned)((total + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0, st,
+                     L->blob[0][1], n0, L->blob[1][1], n, metrics_dev, send);
+  LHIP(hipGetLastError());
+  if (const int rc = pp3_comm_allgather_f32(comm, send, gathered, total, stream))
+    return lerr(rc, f + ": " + pp3_comm_last_error());
+  launch_reduce_ranks(L, gathered, world, metrics_dev, st);
+  LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_learner_normalizer_update_ranks(pp3_learner_t* L, pp3_comm_t* comm, const float* obs, int64_t rows,
+                                        float count_new, float std_min, float std_max, float* mean,
+                                        float* summed_variance, float* std_dev, void* stream) {
+  const std::string f = "pp3_learner_normalizer_update_ranks";
+  if (!L || !comm || !obs || !mean || !summed_variance || !std_dev) return lerr(PP3_ERR_ARG, f + ": null argument");
+  if (rows < 1) return lerr(PP3_ERR_ARG, f + ": rows must be >= 1");
+  if (!isfinite(count_new) || count_new < (float)rows)
+    return lerr(PP3_ERR_ARG, f + ": count_new must be finite and >= rows");
+  if (!isfinite(std_min) || !isfinite(std_max) || !(std_min > 0.0f) || !(std_min <= std_max))
+    return lerr(PP3_ERR_ARG, f + ": std_min and std_max must be finite, 0 < std_min <= std_max");
+  int world;
+  if (const int rc = check_comm(f, L, comm, &world)) return rc;
+  LHIP(hipSetDevice(L->device));
+  const int in_dim = L->net[0].in_dim;
+  if (const int rc = rank_workspace(f.c_str(), &L->rank_norm, &L->rank_norm_world, world, (size_t)in_dim)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  float* row = L->rank_norm;
+  float* gathered = L->rank_norm + in_dim;
+  const int64_t rpr = (rows + NORM_RANGES - 1) / NORM_RANGES;
+  const int nr = (int)((rows + rpr - 1) / rpr);  // the non-empty ranges, <= NORM_RANGES
+  const dim3 cols((in_dim + NTHREAD - 1) / NTHREAD);
+  hipLaunchKernelGGL(norm_sweep_kernel<0>, dim3(nr), dim3(NTHREAD), 0, st, obs, rows, rpr, in_dim, mean, L->norm_mean,
+                     L->norm_part);
+  hipLaunchKernelGGL(norm_reduce_kernel<0>, dim3(1), dim3(RED_BLOCK), 0, st, L->norm_part, nr, in_dim, count_new, row);
+  LHIP(hipGetLastError());
+  if (const int rc = pp3_comm_allgather_f32(comm, row, gathered, in_dim, stream))
+    return lerr(rc, f + ": " + pp3_comm_last_error());
+  hipLaunchKernelGGL(norm_apply_ranks_kernel<0>, cols, dim3(NTHREAD), 0, st, gathered, world, in_dim, count_new, std_min,
+                     std_max, mean, L->norm_mean, summed_variance, std_dev);
+  hipLaunchKernelGGL(norm_sweep_kernel<1>, dim3(nr), dim3(NTHREAD), 0, st, obs, rows, rpr, in_dim, mean, L->norm_mean,
+                     L->norm_part);
+  hipLaunchKernelGGL(norm_reduce_kernel<1>, dim3(1), dim3(RED_BLOCK), 0, st, L->norm_part, nr, in_dim, count_new, row);
+  LHIP(hipGetLastError());
+  if (const int rc = pp3_comm_allgather_f32(comm, row, gathered, in_dim, stream))
+    return lerr(rc, f + ": " + pp3_comm_last_error());
+  hipLaunchKernelGGL(norm_apply_ranks_kernel<1>, cols, dim3(NTHREAD), 0, st, gathered, world, in_dim, count_new, std_min,
+                     std_max, mean, L->norm_mean, summed_variance, std_dev);
   LHIP(hipGetLastError());
   return PP3_OK;
 }

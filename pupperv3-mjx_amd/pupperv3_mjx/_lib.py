@@ -123,6 +123,17 @@ def load() -> C.CDLL:
         for name in ("pp3_learner_normalizer_update", "pp3_learner_set_env_index", "pp3_ppo_loss_grad_indexed",
                      "pp3_grad_clip"):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, "pp3_learner_allreduce_grads"):  # (the learner across ranks; absent from earlier builds run in A/B)
+        f32 = C.c_float
+        L.pp3_learner_allreduce_grads.argtypes = [vp, vp, vp, vp]
+        L.pp3_learner_reduce_gathered.argtypes = [vp, vp, i32, vp, vp]
+        L.pp3_learner_normalizer_update_ranks.argtypes = [vp, vp, vp, i64, f32, f32, f32, vp, vp, vp, vp]
+        L.pp3_comm_allgather_f32.argtypes = [vp, vp, vp, i64, vp]
+        L.pp3_comm_device.argtypes = [vp]
+        L.pp3_comm_device.restype = i32
+        for name in ("pp3_learner_allreduce_grads", "pp3_learner_reduce_gathered",
+                     "pp3_learner_normalizer_update_ranks", "pp3_comm_allgather_f32"):
+            getattr(L, name).restype = C.c_int
     L.pp3_stream.argtypes = [vp]
     L.pp3_stream.restype = vp
     if hasattr(L, "pp3_event_create"):  # (absent from pre-round-5 builds run in kernel A/B: no host-API step there)
@@ -194,6 +205,8 @@ EXPORTED_SYMBOLS = (
     "pp3_learner_create", "pp3_learner_destroy", "pp3_learner_buffers", "pp3_ppo_loss_grad", "pp3_adam_step",
     "pp3_policy_load_params", "pp3_learn_last_error",
     "pp3_learner_normalizer_update", "pp3_learner_set_env_index", "pp3_ppo_loss_grad_indexed", "pp3_grad_clip",
+    "pp3_learner_allreduce_grads", "pp3_learner_reduce_gathered", "pp3_learner_normalizer_update_ranks",
+    "pp3_comm_allgather_f32", "pp3_comm_device",
     "pp3_stream", "pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy",
     "pp3_set_terrain", "pp3_terrain_slots",
     "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_comm_rank", "pp3_comm_world",

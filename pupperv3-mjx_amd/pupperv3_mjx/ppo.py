@@ -13,8 +13,22 @@ Off by default, the rest of Brax's training_step: the running observation normal
 (`clip_gradients`); `train_iteration(shuffle=, max_grad_norm=, update_normalizer=)` chains them in
 Brax's order.
 
-Not here (follow-ups): learning-rate schedules (`lr` is a per-call argument), bf16 / mixed
-precision, the multi-GPU all-reduce of gradients and statistics.
+Across ranks (one process per GPU, `sharding.Comm`): `train_iteration(..., comm=comm)` is Brax's
+training_step under pmap.  Every rank collects on its own env shard and differentiates its own
+minibatch; `allreduce_gradients(comm)` then replaces the gradients and the metrics by their mean over
+the ranks (jax.lax.pmean) before the clip and Adam, and `update_normalizer(env, comm)` adds every
+rank's rows to the statistics (running_statistics.update's psums).  Both sums are taken in rank order
+from all-gathered contributions (the header's reduction contract), so every rank computes the same
+bits and the replicas stay bit-identical for the life of the job, provided that
+
+  * all ranks start from identical parameters and statistics (the same policy_dict, value_dict,
+    normalizer) and pass the same hyper-parameters, minibatch counts and nsteps;
+  * each rank passes its own key, e.g. `rng.split(key, world)[rank]`, as Brax gives each device its own:
+    the collection noise, the entropy noise and the shuffle then differ per rank, as they should.
+
+The mean over ranks is unweighted (Brax's): shards of unequal size weigh their rows unequally.
+
+Not here (follow-ups): learning-rate schedules (`lr` is a per-call argument), bf16 / mixed precision.
 """
 from __future__ import annotations
 
@@ -96,6 +110,7 @@ class PPOLearner:
         self._metrics = _lib.DeviceBuffer(16, self.device)
         self._gnorm = _lib.DeviceBuffer(4, self.device)  # the last clip_gradients' norm
         self._eps = None  # (key bytes, shape, DeviceBuffer)
+        self._global_rows = (None, {})  # (communicator, {(K, N): rows of all ranks}) behind update_normalizer
         self._env = None  # the env whose stream the last call ran on
         self.t = 0        # Adam steps taken
 
@@ -208,20 +223,46 @@ class PPOLearner:
         idx = np.ascontiguousarray(np.asarray(index, dtype=np.int32).ravel())
         self._check(self._L.pp3_learner_set_env_index(self._h, _vp(idx), idx.size, self._stream(stream)))
 
-    def update_normalizer(self, env, std_min: float = 1e-6, std_max: float = 1e6) -> None:
+    def allreduce_gradients(self, comm, stream=None) -> None:
+        """jax.lax.pmean of the gradients and metrics of the last loss_and_grad over the ranks of
+        `comm` (pp3_learner_allreduce_grads: one all-gather, then the rank-ordered sum), between
+        loss_and_grad and clip_gradients / adam_step.  Every rank must call it; grads() and metrics()
+        then return the rank mean, the same bits on every rank."""
+        self._check(self._L.pp3_learner_allreduce_grads(self._h, comm._h, self._metrics.ptr, self._stream(stream)))
+
+    def _rows_of_all_ranks(self, comm, K: int, N: int) -> int:
+        """The sum over ranks of K * N, from one host comm.allreduce per (K, N): shard sizes are fixed
+        for a communicator's life, so later iterations reuse it."""
+        if self._global_rows[0] is not comm:
+            self._global_rows = (comm, {})
+        cache = self._global_rows[1]
+        if (K, N) not in cache:
+            cache[(K, N)] = int(round(float(comm.allreduce([float(K * N)], "sum")[0])))
+        return cache[(K, N)]
+
+    def update_normalizer(self, env, comm=None, std_min: float = 1e-6, std_max: float = 1e6) -> None:
         """Brax's running_statistics.update with the observations the actor saw in the env's last
-        collect_ppo batch ([K][N][36H]; the bootstrap row is not read), on the env's stream."""
+        collect_ppo batch ([K][N][36H]; the bootstrap row is not read), on the env's stream.  comm:
+        with the rows of every rank's batch (pp3_learner_normalizer_update_ranks; every rank must
+        call it), the count advancing by all ranks' rows."""
         if not self.running_statistics:
             raise ValueError("update_normalizer needs PPOLearner(running_statistics=True)")
         ptr, (K, N, D) = env.ppo_device_batch()["observation"]
         if D != self.in_dim:
             raise ValueError(f"the batch's observations have {D} entries, the networks read {self.in_dim}")
         self._env = _base(env)
-        count = self._count + K * N
         base = self._norm.ptr.value
-        self._check(self._L.pp3_learner_normalizer_update(
-            self._h, C.c_void_p(ptr), K * N, float(np.float32(count)), float(std_min), float(std_max), C.c_void_p(base),
-            C.c_void_p(base + 8 * self.in_dim), C.c_void_p(base + 4 * self.in_dim), self._stream()))
+        state = (C.c_void_p(base), C.c_void_p(base + 8 * self.in_dim), C.c_void_p(base + 4 * self.in_dim))
+        if comm is None:
+            count = self._count + K * N
+            self._check(self._L.pp3_learner_normalizer_update(
+                self._h, C.c_void_p(ptr), K * N, float(np.float32(count)), float(std_min), float(std_max), *state,
+                self._stream()))
+        else:
+            count = self._count + self._rows_of_all_ranks(comm, K, N)
+            self._check(self._L.pp3_learner_normalizer_update_ranks(
+                self._h, comm._h, C.c_void_p(ptr), K * N, float(np.float32(count)), float(std_min), float(std_max),
+                *state, self._stream()))
         self._count = count
 
     def normalizer_state(self) -> Dict[str, Any]:
@@ -278,7 +319,7 @@ class PPOLearner:
     def train_iteration(self, env, state, key, device_policy: DevicePolicy, device_value: DevicePolicy, nsteps: int,
                         num_minibatches: int = 1, num_updates_per_batch: int = 1, lr: float = 3e-4,
                         shuffle: bool = False, max_grad_norm: Optional[float] = None, update_normalizer: bool = False,
-                        **hparams):
+                        comm=None, **hparams):
         """One PPO iteration in Brax's training_step order: collect_ppo with the handles (the old
         parameters and statistics), update_normalizer: the running statistics, then
         num_updates_per_batch passes over num_minibatches minibatches (loss, gradient, max_grad_norm:
@@ -286,7 +327,10 @@ class PPOLearner:
         env ranges, or with shuffle ranges [mb B, (mb + 1) B) of a fresh rng.permutation per pass.
         key -> (collect key, entropy-noise key) by rng.split; with shuffle k_perm = split(entropy-
         noise key)[1] and per pass k_perm, k_u = split(k_perm), the pass's index from k_u.  Returns
-        (state, metrics of the last minibatch, the collect's key chain end)."""
+        (state, metrics of the last minibatch, the collect's key chain end).
+        comm (a sharding.Comm; every rank makes the same call on its own env shard with its own key,
+        see the module docstring): the statistics take every rank's rows, allreduce_gradients runs
+        between the loss and the clip, and the metrics are the mean over ranks."""
         base = _base(env)
         n = base.num_envs
         if n % num_minibatches:
@@ -296,7 +340,7 @@ class PPOLearner:
         gae = {k: hparams[k] for k in ("discount", "gae_lambda", "reward_scaling") if k in hparams}
         state, _, k_out = env.collect_ppo(state, device_policy, device_value, nsteps, k_collect, **gae)
         if update_normalizer:
-            self.update_normalizer(env)
+            self.update_normalizer(env, comm)
         k_perm = rng.split(k_eps, 2, base._partitionable)[1] if shuffle else None
         for _ in range(num_updates_per_batch):
             if shuffle:
@@ -305,6 +349,8 @@ class PPOLearner:
                 self.set_env_index(rng.permutation(k_u, n, base._partitionable))
             for mb in range(num_minibatches):
                 self.loss_and_grad(env, mb * B, B, k_eps, indexed=bool(shuffle), **hparams)
+                if comm is not None:
+                    self.allreduce_gradients(comm)
                 if max_grad_norm is not None:
                     self.clip_gradients(max_grad_norm)
                 self.adam_step(lr)

@@ -241,6 +241,13 @@ class Comm:
                                                         vp(dst_dev) if dst_dev else None,
                                                         vp(stream) if stream else None))
 
+    def allgather_device(self, send: int, recv: int, count: int, stream: Optional[int] = None) -> None:
+        """pp3_comm_allgather_f32: this rank's `count` f32 at device address `send` to slot `rank` of
+        `recv` ([world][count] on this device) on every rank, on `stream`, with no host synchronisation."""
+        self._lib.check_comm(self._L.pp3_comm_allgather_f32(self._h, C.c_void_p(send) if send else None,
+                                                            C.c_void_p(recv) if recv else None, int(count),
+                                                            C.c_void_p(stream) if stream else None))
+
     def allreduce(self, values, op: str = "max") -> np.ndarray:
         from . import _abi
         v = np.ascontiguousarray(values, dtype=np.float64).ravel()

@@ -12,6 +12,12 @@ between device events, medians over `--repeat` alternating rounds with the run-t
       below the bound (norm only) and above it (norm and scaling); (a) through
       pp3_ppo_loss_grad_indexed on a permutation of the envs.  Skipped on a library without them.
 "plain_grad_crc32" / "rollout_crc32" (the first plain loss's gradients and metrics; an untimed
+  (f) across ranks, on this one GPU: pp3_learner_allreduce_grads over a ONE-rank RCCL communicator (pack,
+      all-gather, reduce kernel); the reduce kernel alone on a resident [8][count] buffer
+      (pp3_learner_reduce_gathered, world 8); pp3_learner_normalizer_update_ranks over the same
+      communicator beside (e)'s update without one; in rounds of their own after those of (a)-(e), each
+      also as a share of (a)'s minibatch step and of (c).  RCCL between devices is not measured here.
+      Skipped on a library without them.
 rollout's outputs) compare the plain path's result bits between two builds (PP3_LIB_PATH).
 One child process under a time limit.
 
@@ -179,6 +185,32 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
         learner._env = env
         learner.set_env_index(rng.permutation(rng.PRNGKey(3), E))
 
+    # across ranks: a one-rank communicator (made after the rounds of (a)-(e), which so run in the process
+    # they ran in before), a resident [8][count] buffer, a normaliser state of its own
+    ranks = extra and hasattr(raw_lib, "pp3_learner_allreduce_grads")
+    if ranks:
+        from pupperv3_mjx import sharding
+        comm = None
+        count = learner.buffer(0, 1)[1] + learner.buffer(1, 1)[1] + 4
+        gathered = _lib.DeviceBuffer(4 * 8 * count)
+        gathered.upload(rs.normal(scale=1e-2, size=(8, count)).astype(np.float32))
+        rmetrics = _lib.DeviceBuffer(16)
+        rstate = _lib.DeviceBuffer(12 * D)
+        rstate.upload(np.stack([np.zeros(D), np.zeros(D), np.ones(D)]).astype(np.float32))
+        rcount = [0]
+
+        def reduce8():
+            rc = raw_lib.pp3_learner_reduce_gathered(learner._h, gathered.ptr, 8, rmetrics.ptr, stream)
+            assert rc == 0, raw_lib.pp3_learn_last_error()
+
+        def norm_update_ranks():
+            rcount[0] += rows
+            b = rstate.ptr.value
+            rc = raw_lib.pp3_learner_normalizer_update_ranks(
+                learner._h, comm._h, C.c_void_p(obs_ptr), rows, float(np.float32(rcount[0])), 1e-6, 1e6, C.c_void_p(b),
+                C.c_void_p(b + 4 * D), C.c_void_p(b + 8 * D), stream)
+            assert rc == 0, raw_lib.pp3_learn_last_error()
+
     names = ("learn_minibatch_ms", "learn_batch_ms", "reload_ms", "rollout_ms", "torch_minibatch_ms", "torch_batch_ms")
     if extra:
         names += ("norm_update_ms", "torch_norm_ms", "clip_norm_only_ms", "clip_scale_ms", "learn_minibatch_indexed_ms",
@@ -197,6 +229,18 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
         if r >= 2:
             for k, v in got.items():
                 out[k].append(round(v, 4))
+    if ranks:  # (f): its own alternating rounds, the plain update again beside the ranks one
+        comm = sharding.Comm(0, 1, 0, tag=f"_learn_bench{os.getpid()}")
+        rnames = ("allreduce_one_rank_ms", "norm_update_ranks_ms", "norm_update_beside_ranks_ms", "reduce_world8_ms")
+        out.update({k: [] for k in rnames})
+        for r in range(R + 2):
+            learner.loss_and_grad(env, 0, MB, k_eps)  # (the world-8 reduce overwrote the gradients)
+            got = dict(allreduce_one_rank_ms=timed(lambda: learner.allreduce_gradients(comm)),
+                       norm_update_ranks_ms=timed(norm_update_ranks), norm_update_beside_ranks_ms=timed(norm_update),
+                       reduce_world8_ms=timed(reduce8))
+            if r >= 2:
+                for k, v in got.items():
+                    out[k].append(round(v, 4))
     med = {k: sorted(x)[len(x) // 2] for k, x in out.items()}
     spread = {k: [min(x), max(x)] for k, x in out.items()}
     final = learner.metrics()
@@ -212,10 +256,21 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
                           "indexed_over_plain": {"minibatch": round(med["learn_minibatch_indexed_ms"] / med["learn_minibatch_ms"], 3),
                                                  "batch": round(med["learn_batch_indexed_ms"] / med["learn_batch_ms"], 3)},
                           "norm_first_update_vs_torch": norm_check} if extra else {}),
+                      **({"across_ranks": {
+                          "reduced_floats_per_rank": count, "reduce_world8_gb_per_s": round(
+                              9 * count * 4 / (med["reduce_world8_ms"] * 1e6), 1),
+                          "norm_update_ranks_over_plain": round(
+                              med["norm_update_ranks_ms"] / med["norm_update_beside_ranks_ms"], 3),
+                          "share_of_minibatch_step": {k: round(med[k] / med["learn_minibatch_ms"], 4) for k in rnames},
+                          "share_of_rollout": {k: round(med[k] / med["rollout_ms"], 5) for k in rnames}}}
+                         if ranks else {}),
                       "plain_grad_crc32": plain_crc, "rollout_crc32": rollout_crc,
                       "first_total_loss": {"learner": ours, "torch": theirs},
                       "losses_finite": bool(all(np.isfinite(v) for v in final.values()))}), flush=True)
     nstate.free()
+    if ranks:
+        gathered.free(), rmetrics.free(), rstate.free()
+        comm.close()
     for e in ev:
         raw_lib.hipEventDestroy(e)
     actor.close()
