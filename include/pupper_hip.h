@@ -768,6 +768,50 @@ int pp3_learner_reduce_gathered(pp3_learner_t* learner, const float* gathered_de
 int pp3_learner_normalizer_update_ranks(pp3_learner_t* learner, pp3_comm_t* comm, const float* obs, int64_t rows,
                                         float count_new, float std_min, float std_max, float* mean,
                                         float* summed_variance, float* std_dev, void* stream);
+
+/* ---- PPO learner: entropy noise and minibatch shuffle drawn on the device (additive; ABI stays 2) ----
+ * The two random inputs of an iteration that pupperv3_mjx/rng.py draws on the host, restated on the
+ * device from the sampling head's threefry (csrc/pp3_mlp.h), in both jax_threefry_partitionable
+ * layouts (`partitionable` != 0: jax 0.5's default).  Both are enqueued on `stream` with no host copy
+ * and no host synchronisation; a call repeated with the same key gives the same bits.  Errors are
+ * PP3_ERR_ARG through pp3_learn_last_error() before any GPU work, outputs untouched.
+ *
+ * pp3_learner_draw_noise: jax.random.normal(key, (nsteps, num_envs, 12)) into a buffer the learner owns
+ * (allocated at the first call, grown when a call needs more, freed by pp3_learner_destroy; a later
+ * call overwrites it, and one that grows it waits for the queued work that reads the old one), whose
+ * device address it returns in *eps_dev_out: the `eps` of pp3_ppo_loss_grad*.  With count = nsteps *
+ * num_envs * 12, flat element i is
+ *   1.41421356f * erfinvf(u_i),  u_i = jax.random.uniform(key, (count,), minval = nextafter(-1, 0), maxval = 1)[i]
+ * in f32 without FMA contraction: the sampling head's recipe, one thread per element.  u_i is jax's bit
+ * for bit; erfinvf is the device library's, so the values agree with rng.normal (scipy's float64 erfinv
+ * rounded to f32) and with XLA to f32 rounding, not bitwise.
+ * PP3_ERR_ARG: a null pointer, nsteps < 1, num_envs < 1, count >= 2^31.
+ *
+ * pp3_permute_by_bits: x := x[stable_argsort(bits)] in place, bits_dev uint32 [n] and x_dev int32 [n] on
+ * `device`: one round of jax's _shuffle, exposed so that equal bits can be tested.  One workgroup sorts
+ * the 64-bit keys (bits[i] << 32) | i, padded to a power of two with all-ones keys, in a bitonic
+ * network: in LDS for n <= 8192, above that in a global scratch buffer that this call allocates and
+ * frees (it then waits for the sort; the learner's shuffle keeps its own).  PP3_ERR_ARG: a null
+ * pointer, device < 0, n outside 1 .. 65536.
+ *
+ * pp3_learner_shuffle_env_index: jax.random.permutation(key, num_envs) into the learner's env index,
+ * the buffer pp3_learner_set_env_index fills and pp3_ppo_loss_grad_indexed reads (afterwards the index
+ * is set for num_envs), bit for bit rng.permutation:
+ *   rounds = ceil(3 ln(num_envs) / ln(2^32 - 1)) in double  (1 env: 0; up to 1625: 1; up to 65536: 2)
+ *   x = arange(num_envs); per round: key, sub = split(key) on the host;
+ *   bits = random_bits(sub, (num_envs,)) 32-bit words, one thread each;  x := x[stable_argsort(bits)]
+ * PP3_ERR_ARG: a null pointer, num_envs outside 1 .. 65536 (the one-workgroup sort's range).
+ *
+ * pp3_learner_rng_buffers: the device addresses behind the two (tests, checkpoints): the env index and
+ * the entries it is set for (NULL and 0: none set), the noise buffer and its capacity in floats (NULL
+ * and 0: pp3_learner_draw_noise was never called).  PP3_ERR_ARG: a null pointer. */
+int pp3_learner_draw_noise(pp3_learner_t* learner, const uint32_t key[2], int32_t nsteps, int32_t num_envs,
+                           int32_t partitionable, float** eps_dev_out, void* stream);
+int pp3_permute_by_bits(int32_t device, const uint32_t* bits_dev, int32_t n, int32_t* x_dev, void* stream);
+int pp3_learner_shuffle_env_index(pp3_learner_t* learner, const uint32_t key[2], int32_t num_envs,
+                                  int32_t partitionable, void* stream);
+int pp3_learner_rng_buffers(pp3_learner_t* learner, int32_t** index_dev, int32_t* index_n, float** noise_dev,
+                            int64_t* noise_count);
 const char* pp3_learn_last_error(void);
 
 /* ---------------------------------------------------------------------------------------

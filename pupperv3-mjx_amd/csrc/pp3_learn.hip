@@ -22,6 +22,11 @@
 // the three batch-reading kernels read through; NULL is the contiguous range) and the global-norm
 // gradient clip (pp3_grad_clip), all with the same fixed-order sums.
 //
+// The iteration's random inputs, on request drawn here instead of on the host: the entropy noise
+// (pp3_learner_draw_noise: the sampling head's recipe, one thread per element) and the env permutation
+// (pp3_learner_shuffle_env_index: jax's _shuffle, per round a host split, a random-bits kernel and a
+// one-workgroup bitonic sort of (bits << 32) | i; the permute alone: pp3_permute_by_bits).
+//
 // Across ranks (data-parallel PPO over a pp3_comm_t): the gradient blobs and the metrics are packed
 // into one send, all-gathered, and added in rank order by one kernel (pp3_learner_allreduce_grads;
 // the kernel alone: pp3_learner_reduce_gathered); the normaliser's finish is cut in two around an
@@ -597,6 +602,83 @@ __global__ __launch_bounds__(NTHREAD) void repack_kernel(RepackArgs a) {
   }
 }
 
+// ---- the iteration's random inputs on the device: entropy noise and the minibatch shuffle ----
+// (pp3_mlp.h's head_threefry / head_uniform from this translation unit: no kernel elsewhere changes)
+using pp3pol::HeadKey;
+
+// out[i] = jax.random.normal(key, (count,))[i] by the sampling head's recipe
+__global__ __launch_bounds__(NTHREAD) void draw_noise_kernel(HeadKey key, int count, int part, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * NTHREAD + threadIdx.x;
+  if (i >= count) return;
+  const float u = pp3pol::head_uniform(key, count, (int)i, -0x1.fffffep-1f, part);
+  out[i] = 1.41421356f * erfinvf(u);
+}
+
+// bits[i] = jax's 32-bit random_bits(key, (n,))[i] (head_uniform's word, before it becomes a float);
+// iota non-null: also iota[i] = i.  bits null: the iota alone.
+__global__ __launch_bounds__(NTHREAD) void shuffle_bits_kernel(HeadKey key, int n, int part, uint32_t* __restrict__ bits,
+                                                               int32_t* __restrict__ iota) {
+  const int i = blockIdx.x * NTHREAD + threadIdx.x;
+  if (i >= n) return;
+  if (iota) iota[i] = i;
+  if (!bits) return;
+  uint32_t y0, y1, w;
+  if (part) {
+    pp3pol::head_threefry(key.a, key.b, 0u, (uint32_t)i, y0, y1);
+    w = y0 ^ y1;
+  } else {  // the counters 0 .. n-1 (padded to even with a 0) split in halves: x0 = first, x1 = second
+    const int h = (n + (n & 1)) / 2;
+    const int lane = i % h, half = i / h;
+    pp3pol::head_threefry(key.a, key.b, (uint32_t)lane, (lane + h >= n) ? 0u : (uint32_t)(lane + h), y0, y1);
+    w = half ? y1 : y0;
+  }
+  bits[i] = w;
+}
+
+// x := x[stable_argsort(bits)], one workgroup.  The keys are (bits[i] << 32) | i, all distinct, so
+// the order is the stable one whatever the network; slots n .. P-1 (P: n rounded up to a power of
+// two) hold all-ones keys, above every real key (i <= 65535), and end up last.  A bitonic network on
+// the P slots: in LDS while P <= SORT_LDS_KEYS, else in `scratch` [P] in global memory, where the
+// workgroup's barrier orders the passes as it does in LDS.  Then slot i < n takes x[low word]: all
+// gathers read x before the barrier, all stores follow it.
+constexpr int SORT_LDS_KEYS = 8192;  // 64 KiB of 8-byte keys
+constexpr int SORT_MAX_N = 65536;
+
+__device__ __forceinline__ void bitonic_sort_gather(uint64_t* __restrict__ k, const uint32_t* __restrict__ bits, int n, int P,
+                                                    int32_t* __restrict__ x) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < P; i += RED_BLOCK) k[i] = i < n ? ((uint64_t)bits[i] << 32) | (uint32_t)i : ~0ull;
+  __syncthreads();
+  for (int len = 2; len <= P; len <<= 1)
+    for (int j = len >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < P / 2; t += RED_BLOCK) {
+        const int lo = 2 * t - (t & (j - 1)), hi = lo + j;  // the pair (lo, lo + j), lo with bit j clear
+        const uint64_t a = k[lo], b = k[hi];
+        const bool up = (lo & len) == 0;
+        if ((a > b) == up) {
+          k[lo] = b;
+          k[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < n; i += RED_BLOCK) k[i] = (uint32_t)x[(uint32_t)k[i]];
+  __syncthreads();
+  for (int i = tid; i < n; i += RED_BLOCK) x[i] = (int32_t)(uint32_t)k[i];
+}
+
+__global__ __launch_bounds__(RED_BLOCK) void permute_lds_kernel(const uint32_t* __restrict__ bits, int n, int P,
+                                                                int32_t* __restrict__ x) {
+  __shared__ uint64_t keys[SORT_LDS_KEYS];
+  bitonic_sort_gather(keys, bits, n, P, x);
+}
+
+__global__ __launch_bounds__(RED_BLOCK) void permute_global_kernel(const uint32_t* __restrict__ bits, int n, int P,
+                                                                   int32_t* __restrict__ x, uint64_t* __restrict__ scratch) {
+  bitonic_sort_gather(scratch, bits, n, P, x);
+}
+
 struct NetShape {
   int n_layers, in_dim;
   int K[PP3_POLICY_MAX_LAYERS], M[PP3_POLICY_MAX_LAYERS], act[PP3_POLICY_MAX_LAYERS];
@@ -635,6 +717,14 @@ struct pp3_learner {
   int32_t* idx_host[2];
   hipEvent_t idx_ev[2];
   int idx_cap, idx_n, idx_turn;  // allocated entries; entries set (0: none); the next staging block
+  // The device draws (allocated at first use, grown on demand): the entropy noise of
+  // pp3_learner_draw_noise, and the shuffle's random words [cap] and, past SORT_LDS_KEYS envs, its
+  // sort keys [cap rounded up to a power of two].
+  float* noise;
+  int64_t noise_cap;
+  uint32_t* shuf_bits;
+  uint64_t* shuf_keys;
+  int shuf_cap;
 };
 
 static thread_local std::string g_lerr;
@@ -746,6 +836,23 @@ static void free_env_index(pp3_learner* L) {
   if (L->idx_dev) (void)hipFree(L->idx_dev);
   L->idx_dev = nullptr;
   L->idx_cap = L->idx_n = 0;
+}
+
+// room for num_envs entries in the index's device copy and staging blocks
+static int reserve_env_index(pp3_learner* L, int32_t num_envs, const char* fn) {
+  if (num_envs <= L->idx_cap) return PP3_OK;
+  free_env_index(L);  // (hipFree waits for the queued work that reads the old copy)
+  const size_t bytes = (size_t)num_envs * sizeof(int32_t);
+  bool ok = hipMalloc(&L->idx_dev, bytes) == hipSuccess;
+  for (int i = 0; i < 2; i++)
+    ok = ok && hipHostMalloc(&L->idx_host[i], bytes, hipHostMallocDefault) == hipSuccess &&
+         hipEventCreateWithFlags(&L->idx_ev[i], hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    free_env_index(L);
+    return lerr(PP3_ERR_NOMEM, std::string(fn) + ": allocation failed");
+  }
+  L->idx_cap = num_envs;
+  return PP3_OK;
 }
 
 // pp3_ppo_loss_grad (index null) and pp3_ppo_loss_grad_indexed: one path; `fn` names the entry point
@@ -875,6 +982,9 @@ int pp3_learner_destroy(pp3_learner_t* L) {
   float* ws[] = {L->x0, L->y, L->d[0], L->d[1], L->part, L->vs, L->adv, L->row_a, L->row_b, L->stats,
                  L->norm_part, L->norm_mean, L->clip_part, L->rank_grads, L->rank_norm};
   for (float* p : ws) (void)hipFree(p);
+  (void)hipFree(L->noise);
+  (void)hipFree(L->shuf_bits);
+  (void)hipFree(L->shuf_keys);
   free_env_index(L);
   delete L;
   return PP3_OK;
@@ -906,19 +1016,7 @@ int pp3_learner_set_env_index(pp3_learner_t* L, const int32_t* index_host, int32
     if (index_host[i] < 0 || index_host[i] >= num_envs)
       return lerr(PP3_ERR_ARG, "pp3_learner_set_env_index: entry " + std::to_string(i) + " is outside [0, num_envs)");
   LHIP(hipSetDevice(L->device));
-  if (num_envs > L->idx_cap) {  // (hipFree waits for the queued work that reads the old copy)
-    free_env_index(L);
-    const size_t bytes = (size_t)num_envs * sizeof(int32_t);
-    bool ok = hipMalloc(&L->idx_dev, bytes) == hipSuccess;
-    for (int i = 0; i < 2; i++)
-      ok = ok && hipHostMalloc(&L->idx_host[i], bytes, hipHostMallocDefault) == hipSuccess &&
-           hipEventCreateWithFlags(&L->idx_ev[i], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-      free_env_index(L);
-      return lerr(PP3_ERR_NOMEM, "pp3_learner_set_env_index: allocation failed");
-    }
-    L->idx_cap = num_envs;
-  }
+  if (const int rc = reserve_env_index(L, num_envs, "pp3_learner_set_env_index")) return rc;
   const int s = L->idx_turn;
   LHIP(hipEventSynchronize(L->idx_ev[s]));  // the copy that last read this staging block (none: returns at once)
   const size_t bytes = (size_t)num_envs * sizeof(int32_t);
@@ -968,6 +1066,149 @@ int pp3_learner_normalizer_update(pp3_learner_t* L, const float* obs, int64_t ro
   hipLaunchKernelGGL(norm_finish_kernel<1>, dim3(1), dim3(RED_BLOCK), 0, st, L->norm_part, nr, in_dim, count_new,
                      std_min, std_max, mean, L->norm_mean, summed_variance, std_dev);
   LHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+}  // extern "C"
+
+// ---- the device draws ----
+// Host restatement of threefry and of `key, sub = split(key)` (pp3_env.hip's host_threefry is the
+// model), for the shuffle's per-round keys.
+static void learn_host_threefry(uint32_t k0, uint32_t k1, uint32_t x0, uint32_t x1, uint32_t& y0, uint32_t& y1) {
+  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
+  static const int rot[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
+  x0 += k0;
+  x1 += k1;
+  for (int i = 0; i < 5; i++) {
+    for (int q = 0; q < 4; q++) {
+      x0 += x1;
+      x1 = (x1 << rot[i & 1][q]) | (x1 >> (32 - rot[i & 1][q]));
+      x1 ^= x0;
+    }
+    x0 += ks[(i + 1) % 3];
+    x1 += ks[(i + 2) % 3] + (uint32_t)(i + 1);
+  }
+  y0 = x0;
+  y1 = x1;
+}
+// key, sub = jax.random.split(key)
+static void learn_host_split(HeadKey& key, HeadKey& sub, int part) {
+  uint32_t a0, a1, b0, b1;
+  if (part) {
+    learn_host_threefry(key.a, key.b, 0u, 0u, a0, a1);
+    learn_host_threefry(key.a, key.b, 0u, 1u, b0, b1);
+    key = HeadKey{a0, a1};
+    sub = HeadKey{b0, b1};
+  } else {  // flat words [y0(0,2), y0(1,3), y1(0,2), y1(1,3)]: key i = words 2i, 2i + 1
+    learn_host_threefry(key.a, key.b, 0u, 2u, a0, a1);
+    learn_host_threefry(key.a, key.b, 1u, 3u, b0, b1);
+    key = HeadKey{a0, b0};
+    sub = HeadKey{a1, b1};
+  }
+}
+
+static int sort_slots(int n) {
+  int P = 2;
+  while (P < n) P <<= 1;
+  return P;
+}
+
+// x := x[stable_argsort(bits)]; keys: [sort_slots(n)] when n > SORT_LDS_KEYS
+static void launch_permute(const uint32_t* bits, int n, int32_t* x, uint64_t* keys, hipStream_t st) {
+  const int P = sort_slots(n);
+  if (P <= SORT_LDS_KEYS) hipLaunchKernelGGL(permute_lds_kernel, dim3(1), dim3(RED_BLOCK), 0, st, bits, n, P, x);
+  else hipLaunchKernelGGL(permute_global_kernel, dim3(1), dim3(RED_BLOCK), 0, st, bits, n, P, x, keys);
+}
+
+extern "C" {
+
+int pp3_learner_draw_noise(pp3_learner_t* L, const uint32_t* key, int32_t nsteps, int32_t num_envs, int32_t partitionable,
+                           float** eps_dev_out, void* stream) {
+  if (!L || !key || !eps_dev_out) return lerr(PP3_ERR_ARG, "pp3_learner_draw_noise: null argument");
+  if (nsteps < 1 || num_envs < 1) return lerr(PP3_ERR_ARG, "pp3_learner_draw_noise: nsteps and num_envs must be >= 1");
+  const int64_t rows = (int64_t)nsteps * num_envs;
+  if (rows > INT32_MAX / NU) return lerr(PP3_ERR_ARG, "pp3_learner_draw_noise: nsteps * num_envs * 12 must be below 2^31");
+  const int64_t count = rows * NU;
+  LHIP(hipSetDevice(L->device));
+  if (count > L->noise_cap) {  // (hipFree waits for the queued work that reads the old buffer)
+    (void)hipFree(L->noise);
+    L->noise = nullptr;
+    L->noise_cap = 0;
+    if (hipMalloc(&L->noise, (size_t)count * sizeof(float)) != hipSuccess)
+      return lerr(PP3_ERR_NOMEM, "pp3_learner_draw_noise: device allocation failed");
+    L->noise_cap = count;
+  }
+  hipLaunchKernelGGL(draw_noise_kernel, dim3((unsigned)((count + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0,
+                     (hipStream_t)stream, HeadKey{key[0], key[1]}, (int)count, partitionable ? 1 : 0, L->noise);
+  LHIP(hipGetLastError());
+  *eps_dev_out = L->noise;
+  return PP3_OK;
+}
+
+int pp3_permute_by_bits(int32_t device, const uint32_t* bits_dev, int32_t n, int32_t* x_dev, void* stream) {
+  if (!bits_dev || !x_dev) return lerr(PP3_ERR_ARG, "pp3_permute_by_bits: null argument");
+  if (device < 0) return lerr(PP3_ERR_ARG, "pp3_permute_by_bits: device");
+  if (n < 1 || n > SORT_MAX_N) return lerr(PP3_ERR_ARG, "pp3_permute_by_bits: n must be in 1 .. 65536");
+  LHIP(hipSetDevice(device));
+  uint64_t* keys = nullptr;
+  if (n > SORT_LDS_KEYS && hipMalloc(&keys, (size_t)sort_slots(n) * sizeof(uint64_t)) != hipSuccess)
+    return lerr(PP3_ERR_NOMEM, "pp3_permute_by_bits: device allocation failed");
+  launch_permute(bits_dev, n, x_dev, keys, (hipStream_t)stream);
+  const hipError_t e = hipGetLastError();
+  if (keys) (void)hipFree(keys);  // (waits for the sort that uses them)
+  LHIP(e);
+  return PP3_OK;
+}
+
+int pp3_learner_shuffle_env_index(pp3_learner_t* L, const uint32_t* key, int32_t num_envs, int32_t partitionable,
+                                  void* stream) {
+  if (!L || !key) return lerr(PP3_ERR_ARG, "pp3_learner_shuffle_env_index: null argument");
+  if (num_envs < 1 || num_envs > SORT_MAX_N)
+    return lerr(PP3_ERR_ARG, "pp3_learner_shuffle_env_index: num_envs must be in 1 .. 65536");
+  LHIP(hipSetDevice(L->device));
+  const int n = num_envs, part = partitionable ? 1 : 0;
+  if (const int rc = reserve_env_index(L, n, "pp3_learner_shuffle_env_index")) return rc;
+  if (n > L->shuf_cap) {  // (hipFree waits for the queued work that uses the old ones)
+    (void)hipFree(L->shuf_bits);
+    (void)hipFree(L->shuf_keys);
+    L->shuf_bits = nullptr;
+    L->shuf_keys = nullptr;
+    L->shuf_cap = 0;
+    bool ok = hipMalloc(&L->shuf_bits, (size_t)n * sizeof(uint32_t)) == hipSuccess;
+    if (n > SORT_LDS_KEYS) ok = ok && hipMalloc(&L->shuf_keys, (size_t)sort_slots(n) * sizeof(uint64_t)) == hipSuccess;
+    if (!ok) {
+      (void)hipFree(L->shuf_bits);
+      (void)hipFree(L->shuf_keys);
+      L->shuf_bits = nullptr;
+      L->shuf_keys = nullptr;
+      return lerr(PP3_ERR_NOMEM, "pp3_learner_shuffle_env_index: device allocation failed");
+    }
+    L->shuf_cap = n;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int rounds = (int)ceil(3.0 * log((double)n) / log(4294967295.0));
+  const dim3 grid((n + NTHREAD - 1) / NTHREAD), block(NTHREAD);
+  HeadKey k{key[0], key[1]}, sub{0u, 0u};
+  if (rounds == 0) hipLaunchKernelGGL(shuffle_bits_kernel, grid, block, 0, st, sub, n, part, (uint32_t*)nullptr, L->idx_dev);
+  for (int r = 0; r < rounds; r++) {
+    learn_host_split(k, sub, part);
+    hipLaunchKernelGGL(shuffle_bits_kernel, grid, block, 0, st, sub, n, part, L->shuf_bits,
+                       r == 0 ? L->idx_dev : (int32_t*)nullptr);
+    launch_permute(L->shuf_bits, n, L->idx_dev, L->shuf_keys, st);
+  }
+  LHIP(hipGetLastError());
+  L->idx_n = n;
+  return PP3_OK;
+}
+
+int pp3_learner_rng_buffers(pp3_learner_t* L, int32_t** index_dev, int32_t* index_n, float** noise_dev,
+                            int64_t* noise_count) {
+  if (!L || !index_dev || !index_n || !noise_dev || !noise_count)
+    return lerr(PP3_ERR_ARG, "pp3_learner_rng_buffers: null argument");
+  *index_dev = L->idx_n ? L->idx_dev : nullptr;
+  *index_n = L->idx_n;
+  *noise_dev = L->noise;
+  *noise_count = L->noise_cap;
   return PP3_OK;
 }
 

@@ -36,6 +36,7 @@ ERR_ARG, ERR_MODEL, ERR_HIP, ERR_NOMEM, ERR_COMM = 1, 2, 3, 4, 5
 COMM_ID_BYTES = 128  # PP3_COMM_ID_BYTES (ncclUniqueId)
 REDUCE_SUM, REDUCE_MAX = 0, 1
 LEARN_MAX_WORLD = 64  # PP3_LEARN_MAX_WORLD: ranks of the learner's rank-ordered reduces
+SHUFFLE_MAX_ENVS = 65536  # pp3_permute_by_bits / pp3_learner_shuffle_env_index: the one-workgroup sort's range
 
 DR_FRICTION, DR_KP, DR_KD, DR_BASE_IPOS, DR_INERTIA, DR_MASS = 0, 1, 2, 3, 6, 48
 

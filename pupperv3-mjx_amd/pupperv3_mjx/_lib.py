@@ -134,6 +134,14 @@ def load() -> C.CDLL:
         for name in ("pp3_learner_allreduce_grads", "pp3_learner_reduce_gathered",
                      "pp3_learner_normalizer_update_ranks", "pp3_comm_allgather_f32"):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, "pp3_learner_draw_noise"):  # (the device draws; absent from earlier builds run in kernel A/B)
+        L.pp3_learner_draw_noise.argtypes = [vp, vp, i32, i32, i32, C.POINTER(vp), vp]
+        L.pp3_permute_by_bits.argtypes = [i32, vp, i32, vp, vp]
+        L.pp3_learner_shuffle_env_index.argtypes = [vp, vp, i32, i32, vp]
+        L.pp3_learner_rng_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i64)]
+        for name in ("pp3_learner_draw_noise", "pp3_permute_by_bits", "pp3_learner_shuffle_env_index",
+                     "pp3_learner_rng_buffers"):
+            getattr(L, name).restype = C.c_int
     L.pp3_stream.argtypes = [vp]
     L.pp3_stream.restype = vp
     if hasattr(L, "pp3_event_create"):  # (absent from pre-round-5 builds run in kernel A/B: no host-API step there)
@@ -207,6 +215,7 @@ EXPORTED_SYMBOLS = (
     "pp3_learner_normalizer_update", "pp3_learner_set_env_index", "pp3_ppo_loss_grad_indexed", "pp3_grad_clip",
     "pp3_learner_allreduce_grads", "pp3_learner_reduce_gathered", "pp3_learner_normalizer_update_ranks",
     "pp3_comm_allgather_f32", "pp3_comm_device",
+    "pp3_learner_draw_noise", "pp3_permute_by_bits", "pp3_learner_shuffle_env_index", "pp3_learner_rng_buffers",
     "pp3_stream", "pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy",
     "pp3_set_terrain", "pp3_terrain_slots",
     "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_comm_rank", "pp3_comm_world",

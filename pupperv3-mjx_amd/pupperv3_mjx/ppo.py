@@ -28,6 +28,14 @@ bits and the replicas stay bit-identical for the life of the job, provided that
 
 The mean over ranks is unweighted (Brax's): shards of unequal size weigh their rows unequally.
 
+The two random inputs of an iteration, the entropy noise rng.normal(k_eps, (K, N, 12)) and each update
+pass's rng.permutation(k_u, N), are drawn on the host and uploaded by default.  `device_rng=True`
+(`train_iteration`, `loss_and_grad`; `draw_entropy_noise`, `shuffle_env_index`) draws both on the
+device from the same keys, stream-ordered with no host copy; the scalar key splits stay on the host.
+The index is bit-identical to the host path's.  The noise agrees with it to erfinvf rounding: its
+uniform is jax's bit for bit on both paths, then the host path rounds scipy's float64 erfinv to f32
+where the device evaluates the device library's erfinvf, and neither is bit-pinned to XLA's erf_inv.
+
 Not here (follow-ups): learning-rate schedules (`lr` is a per-call argument), bf16 / mixed precision.
 """
 from __future__ import annotations
@@ -110,6 +118,7 @@ class PPOLearner:
         self._metrics = _lib.DeviceBuffer(16, self.device)
         self._gnorm = _lib.DeviceBuffer(4, self.device)  # the last clip_gradients' norm
         self._eps = None  # (key bytes, shape, DeviceBuffer)
+        self._dev_eps = None  # ((key bytes, shape, layout, env), device address): the draw the learner's noise buffer holds
         self._global_rows = (None, {})  # (communicator, {(K, N): rows of all ranks}) behind update_normalizer
         self._env = None  # the env whose stream the last call ran on
         self.t = 0        # Adam steps taken
@@ -202,16 +211,72 @@ class PPOLearner:
             self._eps = (tag, buf)
         return self._eps[1].ptr.value
 
-    def loss_and_grad(self, env, e0: int, B: int, eps_key, indexed: bool = False, **hparams) -> None:
+    def draw_entropy_noise(self, env, key, shape) -> int:
+        """jax.random.normal(key, shape = (K, N, 12)) drawn on the device into the learner's noise
+        buffer (pp3_learner_draw_noise), on the env's stream; returns the device address, the `eps`
+        of loss_and_grad_device.  The next draw overwrites it."""
+        K, N, nu = (int(s) for s in shape)
+        if nu != _abi.NU:
+            raise ValueError(f"the entropy noise has shape (K, N, {_abi.NU})")
+        env = _base(env)
+        self._env = env
+        k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+        out = C.c_void_p()
+        self._check(self._L.pp3_learner_draw_noise(self._h, _vp(k), K, N, int(bool(env._partitionable)), C.byref(out),
+                                                   self._stream()))
+        self._dev_eps = None  # (the buffer no longer holds what a cached draw put there)
+        return out.value
+
+    def _dev_eps_for(self, env, eps_key, shape) -> int:
+        """_eps_for on the device: one draw per (key, shape), shared by an iteration's minibatches.
+        The env is part of the tag: the draw is ordered on that env's stream only, so a call on
+        another env draws again on its own stream."""
+        k = np.asarray(eps_key, dtype=np.uint32).reshape(2)
+        tag = (k.tobytes(), tuple(shape), bool(env._partitionable), env)  # (the env itself: an id could be reused)
+        if self._dev_eps is None or self._dev_eps[0] != tag:
+            self._dev_eps = (tag, self.draw_entropy_noise(env, k, shape))
+        return self._dev_eps[1]
+
+    def shuffle_env_index(self, key, n: int, partitionable: Optional[bool] = None, stream=None) -> None:
+        """jax.random.permutation(key, n) drawn on the device into the env index behind
+        loss_and_grad(indexed=True) (pp3_learner_shuffle_env_index): rng.permutation's bits with no
+        host copy.  partitionable, stream: by default those of the env the last call ran on (else
+        jax 0.5's layout, the default stream)."""
+        if partitionable is None:
+            partitionable = self._env._partitionable if self._env is not None else True
+        k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+        self._check(self._L.pp3_learner_shuffle_env_index(self._h, _vp(k), int(n), int(bool(partitionable)),
+                                                          self._stream(stream)))
+
+    def rng_buffers(self) -> Dict[str, Tuple[Optional[int], int]]:
+        """{"index": (device address or None, entries set), "noise": (device address or None, floats
+        allocated)}: the env index and the device-drawn noise (pp3_learner_rng_buffers)."""
+        ip, n, zp, cnt = C.c_void_p(), C.c_int32(), C.c_void_p(), C.c_int64()
+        self._check(self._L.pp3_learner_rng_buffers(self._h, C.byref(ip), C.byref(n), C.byref(zp), C.byref(cnt)))
+        return {"index": (ip.value, n.value), "noise": (zp.value, cnt.value)}
+
+    def env_index(self) -> np.ndarray:
+        """The env index as set_env_index or shuffle_env_index left it, downloaded (waits for the stream)."""
+        ptr, n = self.rng_buffers()["index"]
+        if not n:
+            raise ValueError("no env index is set")
+        self._wait()
+        out = np.empty(n, np.int32)
+        _lib.check(self._L.pp3_memcpy_d2h(_vp(out), C.c_void_p(ptr), out.nbytes))
+        return out
+
+    def loss_and_grad(self, env, e0: int, B: int, eps_key, indexed: bool = False, device_rng: bool = False,
+                      **hparams) -> None:
         """Loss and gradients on envs [e0, e0 + B) of the env's last collect_ppo batch (indexed: on
         the envs index[e0 : e0 + B] of set_env_index), on the env's stream.  hparams: HPARAMS' keys.
-        Results: grads(), metrics()."""
+        device_rng: the entropy noise of eps_key is drawn on the device (draw_entropy_noise) instead of
+        on the host, once per (key, shape) either way.  Results: grads(), metrics()."""
         dev = env.ppo_device_batch()
         ptr, (K, N, D) = dev["observation"]
         if D != self.in_dim:
             raise ValueError(f"the batch's observations have {D} entries, the networks read {self.in_dim}")
         env = _base(env)
-        eps = self._eps_for(env, eps_key, (K, N, _abi.NU))
+        eps = (self._dev_eps_for if device_rng else self._eps_for)(env, eps_key, (K, N, _abi.NU))
         self._env = env
         self.loss_and_grad_device(K, B, N, e0, ptr, dev["raw_action"][0], dev["log_prob"][0], dev["reward"][0],
                                   dev["done"][0], dev["truncation"][0], eps, env._L.pp3_stream(env._h),
@@ -319,7 +384,7 @@ class PPOLearner:
     def train_iteration(self, env, state, key, device_policy: DevicePolicy, device_value: DevicePolicy, nsteps: int,
                         num_minibatches: int = 1, num_updates_per_batch: int = 1, lr: float = 3e-4,
                         shuffle: bool = False, max_grad_norm: Optional[float] = None, update_normalizer: bool = False,
-                        comm=None, **hparams):
+                        comm=None, device_rng: bool = False, **hparams):
         """One PPO iteration in Brax's training_step order: collect_ppo with the handles (the old
         parameters and statistics), update_normalizer: the running statistics, then
         num_updates_per_batch passes over num_minibatches minibatches (loss, gradient, max_grad_norm:
@@ -328,6 +393,10 @@ class PPOLearner:
         key -> (collect key, entropy-noise key) by rng.split; with shuffle k_perm = split(entropy-
         noise key)[1] and per pass k_perm, k_u = split(k_perm), the pass's index from k_u.  Returns
         (state, metrics of the last minibatch, the collect's key chain end).
+        device_rng: the same keys feed the same draws, on the device: the entropy noise from the
+        entropy-noise key (draw_entropy_noise, once) and each pass's index from its k_u
+        (shuffle_env_index); only the scalar key splits stay on the host.  The index is the host
+        path's bit for bit, the noise agrees with it to erfinvf rounding (module docstring).
         comm (a sharding.Comm; every rank makes the same call on its own env shard with its own key,
         see the module docstring): the statistics take every rank's rows, allreduce_gradients runs
         between the loss and the clip, and the metrics are the mean over ranks."""
@@ -346,9 +415,12 @@ class PPOLearner:
             if shuffle:
                 k_perm, k_u = rng.split(k_perm, 2, base._partitionable)
                 self._env = base
-                self.set_env_index(rng.permutation(k_u, n, base._partitionable))
+                if device_rng:
+                    self.shuffle_env_index(k_u, n, base._partitionable)
+                else:
+                    self.set_env_index(rng.permutation(k_u, n, base._partitionable))
             for mb in range(num_minibatches):
-                self.loss_and_grad(env, mb * B, B, k_eps, indexed=bool(shuffle), **hparams)
+                self.loss_and_grad(env, mb * B, B, k_eps, indexed=bool(shuffle), device_rng=device_rng, **hparams)
                 if comm is not None:
                     self.allreduce_gradients(comm)
                 if max_grad_norm is not None:
@@ -361,6 +433,7 @@ class PPOLearner:
         if getattr(self, "_h", None):
             self._L.pp3_learner_destroy(self._h)
             self._h = None
+            self._dev_eps = None
             for b in (self._norm, self._metrics, self._gnorm, self._eps[1] if self._eps else None):
                 if b is not None:
                     b.free()

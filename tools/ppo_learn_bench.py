@@ -18,6 +18,13 @@ between device events, medians over `--repeat` alternating rounds with the run-t
       communicator beside (e)'s update without one; in rounds of their own after those of (a)-(e), each
       also as a share of (a)'s minibatch step and of (c).  RCCL between devices is not measured here.
       Skipped on a library without them.
+  (g) the iteration's random inputs, in rounds of their own after those of (f): pp3_learner_draw_noise of
+      [K][envs][12] and pp3_learner_shuffle_env_index of `envs` between device events, each also as a
+      share of the sampled rollout timed in the same rounds; the host time (wall clock) of rng.normal
+      and rng.permutation at those shapes and of train_iteration's scalar key splits at one update
+      pass; the whole PPOLearner.train_iteration(shuffle=True, num_minibatches=envs / minibatch) in
+      wall-clock ms from call to return (its closing metrics() waits for the device) with device_rng
+      off and on, alternating.  Skipped on a library without them.
 rollout's outputs) compare the plain path's result bits between two builds (PP3_LIB_PATH).
 One child process under a time limit.
 
@@ -241,6 +248,44 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
             if r >= 2:
                 for k, v in got.items():
                     out[k].append(round(v, 4))
+    device_rng = hasattr(raw_lib, "pp3_learner_draw_noise")
+    if device_rng:  # (g): its own alternating rounds after all of the above, which so run as they ran before
+        import time
+        gnames = ("draw_noise_ms", "shuffle_ms", "rollout_beside_draws_ms", "host_normal_ms", "host_permutation_ms",
+                  "host_key_splits_ms", "train_iteration_host_rng_ms", "train_iteration_device_rng_ms")
+        out.update({k: [] for k in gnames})
+        learner._env = env
+        part = env._partitionable
+
+        def wall(fn):
+            t0 = time.perf_counter()
+            fn()
+            return (time.perf_counter() - t0) * 1e3
+
+        def key_splits(k):  # train_iteration's host key work at one update pass
+            _, k_eps2 = rng.split(k, 2, part)
+            rng.split(rng.split(k_eps2, 2, part)[1], 2, part)
+
+        tkey = [np.array(rng.PRNGKey(4), dtype=np.uint32)]
+        tstate = [st]
+
+        def iteration(on):
+            tstate[0], _, tkey[0] = learner.train_iteration(env, tstate[0], tkey[0], actor, critic, K, num_minibatches=E // MB,
+                                                            shuffle=True, device_rng=on)
+
+        for r in range(R + 2):
+            kr = rng.PRNGKey(100 + r)
+            got = dict(draw_noise_ms=timed(lambda: learner.draw_entropy_noise(env, kr, (K, E, 12))),
+                       shuffle_ms=timed(lambda: learner.shuffle_env_index(kr, E)),
+                       rollout_beside_draws_ms=rollout(),
+                       host_normal_ms=wall(lambda: rng.normal(kr, (K, E, 12), part)),
+                       host_permutation_ms=wall(lambda: rng.permutation(kr, E, part)),
+                       host_key_splits_ms=wall(lambda: key_splits(kr)),
+                       train_iteration_host_rng_ms=wall(lambda: iteration(False)),
+                       train_iteration_device_rng_ms=wall(lambda: iteration(True)))
+            if r >= 2:
+                for k, v in got.items():
+                    out[k].append(round(v, 4))
     med = {k: sorted(x)[len(x) // 2] for k, x in out.items()}
     spread = {k: [min(x), max(x)] for k, x in out.items()}
     final = learner.metrics()
@@ -264,6 +309,17 @@ def child(E: int, W: int, K: int, MB: int, R: int) -> None:
                           "share_of_minibatch_step": {k: round(med[k] / med["learn_minibatch_ms"], 4) for k in rnames},
                           "share_of_rollout": {k: round(med[k] / med["rollout_ms"], 5) for k in rnames}}}
                          if ranks else {}),
+                      **({"device_rng": {
+                          "noise_floats": K * E * 12, "minibatches": E // MB,
+                          "share_of_rollout": {k: round(med[k] / med["rollout_beside_draws_ms"], 5)
+                                               for k in ("draw_noise_ms", "shuffle_ms")},
+                          "host_normal_over_draw": round(med["host_normal_ms"] / med["draw_noise_ms"], 1),
+                          "host_permutation_over_shuffle": round(med["host_permutation_ms"] / med["shuffle_ms"], 1),
+                          "train_iteration_device_over_host_rng": round(
+                              med["train_iteration_device_rng_ms"] / med["train_iteration_host_rng_ms"], 3),
+                          "key_splits_share_of_train_iteration_device_rng": round(
+                              med["host_key_splits_ms"] / med["train_iteration_device_rng_ms"], 4)}}
+                         if device_rng else {}),
                       "plain_grad_crc32": plain_crc, "rollout_crc32": rollout_crc,
                       "first_total_loss": {"learner": ours, "torch": theirs},
                       "losses_finite": bool(all(np.isfinite(v) for v in final.values()))}), flush=True)
