@@ -62,7 +62,7 @@ union alignas(16) Scratch {
   float xipos[NB][3];      // phase 1 (kinematics) -> phase 2 (com_pos)
   struct {                 // phases 3-4
     float F[NV][6];        // crb*cdof -> M entries
-    float cacc[NB][6];     // rne chain -> body forces (overwritten in place by cfrc)
+    float cacc[NB][6];     // the bodies' RNE forces (cfrc): rne_bodies -> bias phase
     float hit_dist[NHIT];  // collision overflow ranking
     int hit_pair[NHIT];
     float con_pos[NC][3];  // collision -> contact Jacobians
@@ -892,6 +892,122 @@ __device__ __forceinline__ int collision(Shared<NC>& s, const DevModel& m, int l
   return l < ncon_h ? sup : 4;
 }
 
+// lane i <- i-1 (row); lane 0 of a row reads 0 (bound_ctrl), as dpp_shr4
+__device__ __forceinline__ float dpp_shr1(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true));
+}
+
+// RNE velocity/acceleration chain (mj_comVel + forward half of mj_rne) and the body forces
+// cinert*cacc + cvel x* (cinert*cvel) behind it, body b on lane b (1..13, com_pos's map): a leg
+// body's parent is lane b - 1 of the same 16-lane DPP row, so each level's cvel / cacc reach the
+// next by one row_shr:1 (level-0 lanes select the base's), and a body's cvel and cacc are still in
+// its lane's registers when its force is made.  Same operations in the same order as walking each
+// leg on one lane.  LDS keeps what other lane maps read: cvel[b], the force (in x.a.cacc[b]: the
+// bias phase's subtree sums) and the whole-tree force sum for the base dofs (cfrc_base).
+template <int NC>
+__device__ __forceinline__ void rne_bodies(Shared<NC>& s, const DevModel& m, int l) {
+  const bool body = l >= 1 && l < NB;
+  const int b = body ? l : 1;
+  const int lev = b >= 2 ? (b - 2) % 3 : -1;  // level in the leg (dof 6+3g+k <-> body 2+3g+k, checked at create)
+  const int dj = b >= 2 ? 4 + b : 6;    // this body's joint dof (base lanes: any row, not used)
+  // one pinned LDS round: this body's cdof row, joint velocity and cinert, then the base's three
+  // rotational cdof rows and six velocities
+  float lcd[6], lqd = s.qvel[dj], ci[10];
+#pragma unroll
+  for (int c = 0; c < 6; c++) lcd[c] = s.cdof[dj][c];
+#pragma unroll
+  for (int c = 0; c < 10; c++) ci[c] = s.cinert[b][c];
+  float bcd[3][6], bq[6];
+#pragma unroll
+  for (int d = 0; d < 3; d++)
+#pragma unroll
+    for (int k = 0; k < 6; k++) bcd[d][k] = s.cdof[3 + d][k];
+#pragma unroll
+  for (int k = 0; k < 6; k++) bq[k] = s.qvel[k];
+  // (gravity as a vector load through an opaque byte offset: a scalar load here would share lgkmcnt
+  // with the LDS round, and as a plain m.gravity[k] the straight-line block makes its address the one
+  // every later reader of gravity shares, an SGPR pair live to the epilogue: two more SGPR spills in
+  // the reset kernels)
+  unsigned goff = (unsigned)(reinterpret_cast<const char*>(m.gravity) - reinterpret_cast<const char*>(&m));
+  asm volatile("" : "+v"(goff));
+  const float* gp = at_bytes(m, goff);
+  float g0 = gp[0], g1 = gp[1], g2 = gp[2];
+  PIN("+v"(g0), "+v"(g1), "+v"(g2));
+  PIN("+v"(lcd[0]), "+v"(lcd[1]), "+v"(lcd[2]), "+v"(lcd[3]), "+v"(lcd[4]), "+v"(lcd[5]), "+v"(lqd), "+v"(ci[0]),
+      "+v"(ci[1]), "+v"(ci[2]), "+v"(ci[3]), "+v"(ci[4]), "+v"(ci[5]), "+v"(ci[6]), "+v"(ci[7]), "+v"(ci[8]), "+v"(ci[9]));
+  PIN("+v"(bcd[0][0]), "+v"(bcd[0][1]), "+v"(bcd[0][2]), "+v"(bcd[0][3]), "+v"(bcd[0][4]), "+v"(bcd[0][5]),
+      "+v"(bcd[1][0]), "+v"(bcd[1][1]), "+v"(bcd[1][2]), "+v"(bcd[1][3]), "+v"(bcd[1][4]), "+v"(bcd[1][5]),
+      "+v"(bcd[2][0]), "+v"(bcd[2][1]), "+v"(bcd[2][2]), "+v"(bcd[2][3]), "+v"(bcd[2][4]), "+v"(bcd[2][5]),
+      "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]));
+  // free joint in closed form (every lane): its translational cdof are the unit vectors (com_pos),
+  // so the velocity after them is (0, v); each rotational dof's cdof_dot = (0, v) x cdof = (0, v x a_d),
+  // hence cacc = (0, -g + v x w) with w = sum_d a_d qvel[3+d], and cvel = (w, v + sum_d b_d qvel[3+d])
+  float w[3] = {0, 0, 0}, bsum[3] = {0, 0, 0};
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const float q = bq[3 + d];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { w[k] += bcd[d][k] * q; bsum[k] += bcd[d][3 + k] * q; }
+  }
+  const float v0 = bq[0], v1 = bq[1], v2 = bq[2];
+  const float cvb[6] = {w[0], w[1], w[2], v0 + bsum[0], v1 + bsum[1], v2 + bsum[2]};
+  const float cab[6] = {0, 0, 0, -g0 + (v1 * w[2] - v2 * w[1]), -g1 + (v2 * w[0] - v0 * w[2]),
+                        -g2 + (v0 * w[1] - v1 * w[0])};
+  // level 0 from the base's, levels 1 and 2 from the parent lane's; a lane keeps the value of its
+  // own level (the base lane the base's)
+  float cv[6], ca[6];
+  {
+    float cdd[6];
+    cross_motion(cdd, cvb, lcd);
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      const float tv = cvb[c] + lcd[c] * lqd, ta = cab[c] + cdd[c] * lqd;
+      cv[c] = lev >= 0 ? tv : cvb[c];
+      ca[c] = lev >= 0 ? ta : cab[c];
+    }
+  }
+#pragma unroll
+  for (int lv = 1; lv < 3; lv++) {
+    // (every DPP source is pinned on all lanes first, as in kinematics)
+    float pv[6], pa[6], cdd[6];
+    PIN("+v"(cv[0]), "+v"(cv[1]), "+v"(cv[2]), "+v"(cv[3]), "+v"(cv[4]), "+v"(cv[5]), "+v"(ca[0]), "+v"(ca[1]),
+        "+v"(ca[2]), "+v"(ca[3]), "+v"(ca[4]), "+v"(ca[5]));
+#pragma unroll
+    for (int c = 0; c < 6; c++) { pv[c] = dpp_shr1(cv[c]); pa[c] = dpp_shr1(ca[c]); }
+    PIN("+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(pv[4]), "+v"(pv[5]), "+v"(pa[0]), "+v"(pa[1]),
+        "+v"(pa[2]), "+v"(pa[3]), "+v"(pa[4]), "+v"(pa[5]));
+    cross_motion(cdd, pv, lcd);
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      const float tv = pv[c] + lcd[c] * lqd, ta = pa[c] + cdd[c] * lqd;
+      cv[c] = lev >= lv ? tv : cv[c];
+      ca[c] = lev >= lv ? ta : ca[c];
+    }
+  }
+  float cf[6];
+  {
+    float f1[6], f2[6], f3[6];
+    mul_inert_vec(f1, ci, ca);
+    mul_inert_vec(f2, ci, cv);
+    cross_force(f3, cv, f2);
+#pragma unroll
+    for (int k = 0; k < 6; k++) cf[k] = body ? f1[k] + f3[k] : 0.0f;
+  }
+  if (body)
+#pragma unroll
+    for (int k = 0; k < 6; k++) { s.cvel[b][k] = cv[k]; s.x.a.cacc[b][k] = cf[k]; }  // cfrc
+  // all six sums first (independent DPP chains interleave), then the stores
+  float t[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) t[k] = hsum_lane16(cf[k]);
+  if (l == 16)
+#pragma unroll
+    for (int k = 0; k < 6; k++) s.cfrc_base[k] = t[k];
+}
+
+// The leg-per-lane form of the same chain and forces (the form before rne_bodies), kept for the one
+// instantiation in which rne_bodies costs an SGPR spill more than it (substep's LEGRNE; the
+// resource tables under profiles/).
 // RNE velocity/acceleration chain (mj_comVel + forward half of mj_rne): lanes 0..3 each
 // walk base -> leg l writing cvel and cacc of its links (lane 0 also the base).  The leg's three
 // cdof rows and joint velocities are loaded (pinned) before the first store: a level's loads
@@ -1593,7 +1709,7 @@ __device__ __attribute__((noinline)) void dense_search(LdsShared<NC>* sp, int l,
 // one physics substep (mj_step): forward + Newton + Euler.  `integrate` = false for reset
 // (mj_forward only).  Must be called by all 64 lanes (both halves).
 // ------------------------------------------------------------------------------------
-template <int NC, int NWV = 1, bool LIBSC = true, bool CULL = false>
+template <int NC, int NWV = 1, bool LIBSC = true, bool CULL = false, bool LEGRNE = false>
 __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, int h, bool integrate_prev,
                                        const KinConst& kc PROF_PARAM, float* ccache = nullptr) {
   constexpr int NR = (Shared<NC>::NEFC + HW - 1) / HW;  // constraint rows per lane
@@ -1624,7 +1740,11 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
   // v22: 28 more registers live through kinematics and com)
   const PairLoad pair_pf = load_pair(m, l < m.npair ? l : 0);
   // ---- phase 3: CRB*cdof, RNE chain, collision, actuation/passive, limit + friction rows ----
-  { crb_times_cdof(s, m, l); rne_chain(s, m, l); SYNC(); }
+  {
+    crb_times_cdof(s, m, l);
+    if constexpr (LEGRNE) rne_chain(s, m, l); else rne_bodies(s, m, l);
+    SYNC();
+  }
   PHASE(15); l = opaque_lane(l);
   int lsup = 4;  // lane c: support of contact c (4 = none)
   { lsup = collision<NC, NWV, CULL>(s, m, l, h, pair_pf, ccache); SYNC(); }
@@ -1735,7 +1855,7 @@ __device__ __forceinline__ int substep(Shared<NC>& s, const DevModel& m, int l, 
     s.M[i][j] = v;
     s.M[j][i] = v;
   }
-  rne_body_forces(s, l, h);
+  if constexpr (LEGRNE) rne_body_forces(s, l, h);
   const int ncon = s.ncon;
   __builtin_assume(ncon >= 0 && ncon <= NC);  // (collision caps it): NC = 8 -> one edge-row pass
   for (int it = l; it < ncon * NV; it += HW) {
@@ -2983,7 +3103,7 @@ __global__ __launch_bounds__(WAVE * NWV, PP3_STEP_WPE) void env_step_kernel(
     const GModel* mp = (const GModel*)(a.m);
     asm volatile("" : "+s"(mp));
     // (the single-step kernel takes sincos_f32, the fused one the library's sincosf: same values)
-    const int wgt = substep<NC, NWV, FUSED, CULL>(s, *(const DevModel*)mp, l, h, f > 0, kc PROF_ARG,
+    const int wgt = substep<NC, NWV, FUSED, CULL, NC == 16 && CULL && !FUSED>(s, *(const DevModel*)mp, l, h, f > 0, kc PROF_ARG,
                                                   CULL ? cull_cache[alias ? 0 : 2 * wv + h] : nullptr);
     heavy = wgt >= HEAVY_WEIGHT ? 1 : 0;
   }
