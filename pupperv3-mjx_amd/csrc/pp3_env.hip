@@ -14,6 +14,12 @@
 // launch (~10 KB per env, 8 waves = 16 envs per CU); HBM sees one read and one write of
 // each env's state record per env step.  18x18 LDL^T runs one matrix row per lane with the
 // pivot column broadcast through LDS; half-wave reductions run on the DPP network.
+//
+// This file is the step library's device code (namespace pp3) plus the thin host layer that
+// launches it: the C-ABI entry points that need a kernel or a device symbol in their translation
+// unit.  With pp3_device.h, pp3_mlp.h and the Makefile it is what decides the kernels, and what the
+// benchmark's kernel source hash covers.  The rest of the ABI is pp3_host.hip, the host model
+// builder pp3_model.hip; what the three share is pp3_env_host.h.
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -3546,578 +3552,71 @@ __global__ void fill_uniform_kernel(float* p, int64_t n, uint32_t seed, uint32_t
 }  // namespace pp3
 
 // ======================================================================================
-// host side: C-ABI
+// host side: the C-ABI entry points that launch a kernel or read a device symbol of this file.
+// The rest of the ABI is pp3_host.hip, the host model builder pp3_model.hip (pp3_env_host.h).
 // ======================================================================================
+#include "pp3_env_host.h"
+
 using namespace pp3;
 
-struct pp3_env {
-  int device;
-  int N;
-  int stride;
-  int H;
-  int La, Li;  // latency rows' lengths (with H: which size caps the step kernels are launched with)
-  hipStream_t stream;
-  DevModel* dmodel;
-  float* state;
-  float* obs;  // [N][36H], updated in place by every step (stable pointer: pp3_field(PP3_F_OBS))
-  float* reward;
-  float* done;
-  float* metrics;
-  float* dr;
-  int dr_on;
-  float* pipe;
-  int pipe_on;
-  int nc;  // contact cap (kernel template): 8 on flat terrain, 16 with obstacle geoms
-  float* action;
-  float* episode;      // auto-reset mode buffers (null when off)
-  float* first_state;
-  float* first_obs;
-  int episode_length;
-  int action_repeat;  // auto-reset mode: launches per wrapper step (1 otherwise)
-  float* terrain;  // TerrainRec rows (pp3_set_terrain), null until first set
-  int nbox;        // world box-geom slots in the model
-  int cull;        // DevModel::cull_on: steps launch env_step_kernel<..., CULL = true>
-  int partitionable;  // the config's rng_partitionable (the sampled policy rollout's host key chain)
-  float* traj_trunc;  // pp3_set_truncation_trajectory: the rollouts' truncation rows (caller's buffer) or null
-  int trunc_steps;    // its capacity in steps
-  hipEvent_t ev0, ev1;
-};
-
-static thread_local std::string g_err;
-static int set_err(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess) return set_err(PP3_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-static void clamp_solimp(const double in[5], float out[5]) {
-  double dmin = in[0], dmax = in[1], width = in[2], mid = in[3], power = in[4];
-  dmin = dmin < 0.0001 ? 0.0001 : dmin > 0.9999 ? 0.9999 : dmin;
-  dmax = dmax < 0.0001 ? 0.0001 : dmax > 0.9999 ? 0.9999 : dmax;
-  width = width < 1e-15 ? 1e-15 : width;
-  mid = mid < 0.0001 ? 0.0001 : mid > 0.9999 ? 0.9999 : mid;
-  power = power < 1 ? 1 : power;
-  out[0] = (float)dmin; out[1] = (float)dmax; out[2] = (float)width; out[3] = (float)mid; out[4] = (float)power;
-}
-static void kb_of(const double solref[2], const double solimp[5], double h, float* k, float* b) {
-  float si[5];
-  clamp_solimp(solimp, si);
-  double dmax = si[1];
-  if (solref[0] > 0) {
-    double tc = solref[0] < 2 * h ? 2 * h : solref[0], dr = solref[1];
-    *k = (float)(1.0 / (dmax * dmax * tc * tc * dr * dr));
-    *b = (float)(2.0 / (dmax * tc));
-  } else {
-    *k = (float)(-solref[0] / (dmax * dmax));
-    *b = (float)(-solref[1] / dmax);
-  }
-}
-static double imp_host(const float si[5], double pos, double margin) {
-  double x = fabs((pos - margin) / si[2]);
-  if (x >= 1) return si[1];
-  if (x <= 0) return si[0];
-  double y;
-  if (si[4] == 1) y = x;
-  else if (x <= si[3]) y = pow(x, si[4]) / pow(si[3], si[4] - 1);
-  else y = 1 - pow(1 - x, si[4]) / pow(1 - si[3], si[4] - 1);
-  return si[0] + y * (si[1] - si[0]);
-}
-
-static void quat2mat_d(const double q[4], double R[9]) {
-  double w = q[0], x = q[1], y = q[2], z = q[3];
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
-  R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-  R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
-}
-
-// the per-lane phase records (pp3_device.h LaneRec) from the already filled model fields
-static void set_i(float& f, int32_t v) { memcpy(&f, &v, 4); }
-template <int N>
-static void put_rec(LaneTab<N>& t, int l, const LaneRec<N>& r) {
-  for (int k = 0; k < N; k++)
-    for (int c = 0; c < 4; c++) t.g[k][l][c] = r.f[4 * k + c];
-}
-static void fill_lane_records(DevModel* d) {
-  for (int l = 0; l < 32; l++) {
-    LaneRec<(LL_WORDS + 3) / 4> rl = {};
-    float* f = rl.f;
-    if (l < 2 * (NJ - 1)) {
-      const int j = 1 + l / 2, hi = l & 1;
-      set_i(f[LL_LIM_ON], d->jnt_limited[j] ? 1 : 0);
-      f[LL_RANGE] = d->jnt_range[j][hi];
-      f[LL_MARGIN] = d->lim_margin[j];
-      f[LL_INVW] = d->lim_invw[j];
-      f[LL_B] = d->lim_b[j];
-      f[LL_K] = d->lim_k[j];
-      for (int k = 0; k < 5; k++) f[LL_SOLIMP + k] = d->lim_solimp[j][k];
-    }
-    if (l < NFR) {
-      f[LL_FR_R] = d->fr_R[6 + l];
-      f[LL_FR_B] = d->fr_b[6 + l];
-    }
-    if (l < NU) {
-      set_i(f[LL_ACT_DOF], d->act_dof[l]);
-      set_i(f[LL_ACT_QADR], d->act_qadr[l]);
-      set_i(f[LL_ACT_FLAGS], (d->act_ctrllimited[l] ? ACTF_CTRLLIMITED : 0) | (d->act_forcelimited[l] ? ACTF_FORCELIMITED : 0) |
-                                 (d->act_biastype[l] == PP3_BIAS_AFFINE ? ACTF_AFFINE : 0));
-      f[LL_CRANGE] = d->act_crange[l][0];
-      f[LL_CRANGE + 1] = d->act_crange[l][1];
-      f[LL_GEAR] = d->act_gear[l];
-      f[LL_GAIN] = d->act_gain[l];
-      for (int k = 0; k < 3; k++) f[LL_BIAS + k] = d->act_bias[l][k];
-      f[LL_FRANGE] = d->act_frange[l][0];
-      f[LL_FRANGE + 1] = d->act_frange[l][1];
-    }
-    LaneRec<(LC_WORDS + 3) / 4> rc = {};
-    float* c = rc.f;
-    if (l >= 1 && l < NB)
-      for (int k = 0; k < 4; k++) c[LC_IQUAT + k] = d->body_iquat[l][k];
-    if (l < d->nrobot_geom) {
-      const int g = d->robot_geom[l];
-      set_i(c[LC_PT_BODY], d->cg_body[g]);
-      for (int k = 0; k < 3; k++) c[LC_PT_POS + k] = d->cg_pos[g][k];
-    } else if (l >= 16 && l < 20) {
-      const int si = d->feet_site[l - 16];
-      set_i(c[LC_PT_BODY], d->site_body[si]);
-      for (int k = 0; k < 3; k++) c[LC_PT_POS + k] = d->site_pos[si][k];
-    }
-    LaneRec<(LM_WORDS + 3) / 4> rm = {};
-    float* mr = rm.f;
-    for (int t = 0; t < 4; t++) {
-      const int p = l + 32 * t;
-      if (p < d->nmpair) {
-        const int i = d->mp_i[p], j = d->mp_j[p];
-        set_i(mr[LM_IJ + t], i | (j << 8));
-        mr[LM_ARM + t] = i == j ? d->dof_armature[i] : 0.0f;
-      } else {
-        set_i(mr[LM_IJ + t], -1);
-      }
-    }
-    if (l < NV) mr[LM_DAMP] = d->dof_damping[l];
-    if (l < NFR) mr[LM_FLOSS] = d->fr_floss[6 + l];
-    LaneRec<(LE_WORDS + 3) / 4> re = {};
-    float* e = re.f;
-    if (l < NU) {
-      e[LE_POSE] = d->default_pose[l];
-      e[LE_JLO] = d->jlo[l];
-      e[LE_JHI] = d->jhi[l];
-      if (l % 3 == 1) e[LE_ABD] = d->des_abd[l / 3];
-    }
-    if (l < 4) set_i(e[LE_LEG], d->lower_leg_body[l]);
-    if (l >= 16 && l < 16 + NU) e[LE_POSE16] = d->default_pose[l - 16];
-    put_rec(d->lane_lim, l, rl);
-    put_rec(d->lane_com, l, rc);
-    put_rec(d->lane_m, l, rm);
-    put_rec(d->lane_env, l, re);
-    LaneRec<(LS_WORDS + 3) / 4> rs = {};
-    float* sr = rs.f;
-    if (l < d->nsensor) {
-      const int sid = d->sensor_objid[l], b = d->site_body[sid];
-      set_i(sr[LS_TYPE], d->sensor_type[l]);
-      set_i(sr[LS_ADR], d->sensor_adr[l]);
-      sr[LS_CUT] = d->sensor_cutoff[l];
-      set_i(sr[LS_BODY], b);
-      for (int k = 0; k < 3; k++) sr[LS_SPOS + k] = d->site_pos[sid][k];
-      for (int k = 0; k < 4; k++) sr[LS_SQUAT + k] = d->site_quat[sid][k];
-      int chain[NB], n = 0;  // (depth checked at create)
-      for (int bb = b; bb > 0 && n < LS_MAXCH; bb = d->body_parent[bb]) chain[n++] = bb;
-      set_i(sr[LS_NCH], n);
-      for (int c = 0; c < n; c++) {  // root first
-        const int bb = chain[n - 1 - c];
-        set_i(sr[LS_CH + 4 * c], bb);
-        set_i(sr[LS_CH + 4 * c + 1], d->body_dofadr[bb]);
-        set_i(sr[LS_CH + 4 * c + 2], d->body_dofnum[bb]);
-        set_i(sr[LS_CH + 4 * c + 3], d->body_parent[bb]);
-      }
-    }
-    put_rec(d->lane_sens, l, rs);
-  }
-  for (int p = 0; p < d->npair; p++) {
-    d->pair_gid[p][0] = (float)d->cg_id[d->pair_g1[p]];
-    d->pair_gid[p][1] = (float)d->cg_id[d->pair_g2[p]];
-  }
-  for (int p = 0; p < d->npair; p++) {
-    const int ga = d->cg_id[d->pair_g1[p]], gb = d->cg_id[d->pair_g2[p]];
-    int kn = 0, bo = 0;
-    for (int i = 0; i < d->n_knee_geoms; i++) kn += (ga == d->knee_geoms[i] || gb == d->knee_geoms[i]) ? 1 : 0;
-    for (int i = 0; i < d->n_torso_geoms; i++) bo += (ga == d->torso_geoms[i] || gb == d->torso_geoms[i]) ? 1 : 0;
-    d->pair_con[p].knee = (float)kn;
-    d->pair_con[p].body = (float)bo;
-  }
-}
-
-static int build_devmodel(const pp3_model_t* mm, const pp3_env_config_t* c, DevModel* d) {
-  memset(d, 0, sizeof(*d));
-  // topology checks (fixed-structure kernel)
-  if (mm->jnt_type[0] != PP3_JNT_FREE || mm->body_parentid[1] != 0) return set_err(PP3_ERR_MODEL, "base must be a free body");
-  for (int l = 0; l < 4; l++)
-    for (int k = 0; k < 3; k++) {
-      int b = 2 + 3 * l + k, j = 1 + 3 * l + k;
-      if (mm->body_parentid[b] != (k == 0 ? 1 : b - 1) || mm->body_jntadr[b] != j || mm->jnt_type[j] != PP3_JNT_HINGE ||
-          mm->jnt_dofadr[j] != 6 + 3 * l + k || mm->jnt_qposadr[j] != 7 + 3 * l + k)
-        return set_err(PP3_ERR_MODEL, "legs must be 4 serial chains of 3 hinge bodies");
-    }
-  if (mm->cone != PP3_CONE_PYRAMIDAL) return set_err(PP3_ERR_MODEL, "only pyramidal cones");
-  for (int j = 1; j < NJ; j++)
-    if (mm->jnt_pos[j][0] != 0 || mm->jnt_pos[j][1] != 0 || mm->jnt_pos[j][2] != 0)
-      return set_err(PP3_ERR_MODEL, "hinge anchors must coincide with body origins (jnt_pos = 0)");
-  if (mm->eulerdamp) {
-    for (int i = 0; i < NV; i++)
-      if (mm->dof_damping[i] > 0) return set_err(PP3_ERR_MODEL, "eulerdamp with joint damping is not supported (xml:58 disables it)");
-  }
-  if (c->obs_history < 1 || c->obs_history > HMAX) return set_err(PP3_ERR_ARG, "observation_history must be in [1, 16]");
-  if (c->latency_len < 1 || c->latency_len > PP3_MAX_LAG || c->imu_latency_len < 1 || c->imu_latency_len > PP3_MAX_LAG)
-    return set_err(PP3_ERR_ARG, "latency distributions must have 1..8 entries");
-  if (c->n_frames < 1) return set_err(PP3_ERR_ARG, "n_frames < 1");
-  const double h = mm->timestep;
-  d->h = (float)h;
-  for (int k = 0; k < 3; k++) d->gravity[k] = (float)mm->gravity[k];
-  d->impratio = (float)mm->impratio;
-  d->gtol_scale = (float)(mm->tolerance * mm->ls_tolerance * mm->meaninertia * NV);
-  d->ls_iterations = mm->ls_iterations;
-  d->iterations = mm->iterations;
-  for (int b = 0; b < NB; b++) {
-    for (int k = 0; k < 3; k++) {
-      d->body_pos[b][k] = (float)mm->body_pos[b][k];
-      d->body_ipos[b][k] = (float)mm->body_ipos[b][k];
-      d->body_inertia[b][k] = (float)mm->body_inertia[b][k];
-    }
-    for (int k = 0; k < 4; k++) {
-      d->body_quat[b][k] = (float)mm->body_quat[b][k];
-      d->body_iquat[b][k] = (float)mm->body_iquat[b][k];
-    }
-    d->body_mass[b] = (float)mm->body_mass[b];
-    uint32_t mask = 0;
-    for (int bb = b; bb > 0; bb = mm->body_parentid[bb])
-      for (int i = 0; i < mm->body_dofnum[bb]; i++) mask |= 1u << (mm->body_dofadr[bb] + i);
-    d->body_dofmask[b] = mask;
-  }
-  for (int i = 0; i < NV; i++) d->dof_body[i] = mm->dof_bodyid[i];
-  for (int j = 0; j < NJ; j++) {
-    for (int k = 0; k < 3; k++) {
-      d->jnt_pos[j][k] = (float)mm->jnt_pos[j][k];
-      d->jnt_axis[j][k] = (float)mm->jnt_axis[j][k];
-    }
-    d->jnt_range[j][0] = (float)mm->jnt_range[j][0];
-    d->jnt_range[j][1] = (float)mm->jnt_range[j][1];
-    d->jnt_limited[j] = mm->jnt_limited[j];
-    kb_of(mm->jnt_solref[j], mm->jnt_solimp[j], h, &d->lim_k[j], &d->lim_b[j]);
-    clamp_solimp(mm->jnt_solimp[j], d->lim_solimp[j]);
-    d->lim_margin[j] = (float)mm->jnt_margin[j];
-    d->lim_invw[j] = (float)mm->dof_invweight0[mm->jnt_dofadr[j]];
-    // both sides of one hinge can only be violated together when the range is narrower than
-    // twice the margin; excluding that bounds the limit rows at one per hinge (NLMAX)
-    if (j > 0 && mm->jnt_limited[j] && !(mm->jnt_range[j][1] - mm->jnt_range[j][0] > 2.0 * mm->jnt_margin[j]))
-      return set_err(PP3_ERR_MODEL, "joint " + std::to_string(j) +
-                                        ": range narrower than twice the margin (both limit sides could be active)");
-  }
-  for (int i = 0; i < NQ; i++) { d->qpos0[i] = (float)mm->qpos0[i]; d->key_qpos[i] = (float)mm->key_qpos[i]; }
-  for (int i = 0; i < NV; i++) {
-    d->dof_armature[i] = (float)mm->dof_armature[i];
-    d->dof_damping[i] = (float)mm->dof_damping[i];
-    d->fr_floss[i] = (float)mm->dof_frictionloss[i];
-    float si[5], k, b;
-    clamp_solimp(mm->dof_solimp[i], si);
-    kb_of(mm->dof_solref[i], mm->dof_solimp[i], h, &k, &b);
-    double imp = imp_host(si, 0.0, 0.0);
-    double R = (1 - imp) / imp * mm->dof_invweight0[i];
-    d->fr_R[i] = (float)(R < 1e-15 ? 1e-15 : R);
-    d->fr_b[i] = b;
-    if (i >= 6 && mm->dof_frictionloss[i] <= 0) return set_err(PP3_ERR_MODEL, "every hinge needs frictionloss > 0 (xml:55)");
-    if (i < 6 && mm->dof_frictionloss[i] > 0) return set_err(PP3_ERR_MODEL, "free-joint frictionloss unsupported");
-  }
-  // M sparsity pairs
-  int np = 0;
-  for (int i = 0; i < NV; i++)
-    for (int j = i; j >= 0; j = mm->dof_parentid[j]) {
-      if (np >= NMPAIR_MAX) return set_err(PP3_ERR_MODEL, "M too dense");
-      d->mp_i[np] = (uint8_t)i;
-      d->mp_j[np] = (uint8_t)j;
-      np++;
-    }
-  d->nmpair = np;
-  if (np != NMPAIR) return set_err(PP3_ERR_MODEL, "mass-matrix sparsity differs from the 13-body quadruped tree");
-  // collision geoms
-  d->ncgeom = mm->ncgeom;
-  int nslot = 0;
-  int box_slot[PP3_MAX_CGEOM];
-  d->nbox = 0;
-  d->terrain = 0;
-  for (int g = 0; g < mm->ncgeom; g++) {
-    box_slot[g] = (mm->cgeom_bodyid[g] == 0 && mm->cgeom_type[g] == PP3_GEOM_BOX) ? d->nbox++ : -1;
-    d->cg_type[g] = mm->cgeom_type[g];
-    d->cg_body[g] = mm->cgeom_bodyid[g];
-    d->cg_id[g] = mm->cgeom_id[g];
-    for (int k = 0; k < 3; k++) d->cg_size[g][k] = (float)mm->cgeom_size[g][k];
-    if (mm->cgeom_bodyid[g] == 0) {
-      d->cg_slot[g] = -1;
-      double R[9];
-      quat2mat_d(mm->cgeom_quat[g], R);
-      for (int k = 0; k < 9; k++) d->cg_wmat[g][k] = (float)R[k];
-      for (int k = 0; k < 3; k++) d->cg_pos[g][k] = (float)mm->cgeom_pos[g][k];
-    } else {
-      if (mm->cgeom_type[g] != PP3_GEOM_SPHERE) return set_err(PP3_ERR_MODEL, "moving collision geoms must be spheres");
-      if (nslot >= NROBOT_GEOM) return set_err(PP3_ERR_MODEL, "too many robot collision geoms (max 8)");
-      d->cg_slot[g] = nslot;
-      d->robot_geom[nslot++] = g;
-      for (int k = 0; k < 3; k++) d->cg_pos[g][k] = (float)mm->cgeom_pos[g][k];
-    }
-  }
-  d->nrobot_geom = nslot;
-  d->npair = mm->npair;
-  for (int p = 0; p < mm->npair; p++) {
-    int g1 = mm->pair_g1[p], g2 = mm->pair_g2[p];
-    d->pair_g1[p] = g1;
-    d->pair_g2[p] = g2;
-    // mj_contactParam
-    double solref[2], solimp[5], mu;
-    int p1 = mm->cgeom_priority[g1], p2 = mm->cgeom_priority[g2];
-    if (p1 != p2) {
-      int g = p1 > p2 ? g1 : g2;
-      mu = mm->cgeom_friction[g][0];
-      for (int k = 0; k < 2; k++) solref[k] = mm->cgeom_solref[g][k];
-      for (int k = 0; k < 5; k++) solimp[k] = mm->cgeom_solimp[g][k];
-    } else {
-      double s1 = mm->cgeom_solmix[g1], s2 = mm->cgeom_solmix[g2], mix;
-      if (s1 >= 1e-15 && s2 >= 1e-15) mix = s1 / (s1 + s2);
-      else if (s1 < 1e-15 && s2 < 1e-15) mix = 0.5;
-      else if (s1 < 1e-15) mix = 0;
-      else mix = 1;
-      if (mm->cgeom_solref[g1][0] > 0 && mm->cgeom_solref[g2][0] > 0)
-        for (int k = 0; k < 2; k++) solref[k] = mix * mm->cgeom_solref[g1][k] + (1 - mix) * mm->cgeom_solref[g2][k];
-      else
-        for (int k = 0; k < 2; k++) solref[k] = fmin(mm->cgeom_solref[g1][k], mm->cgeom_solref[g2][k]);
-      for (int k = 0; k < 5; k++) solimp[k] = mix * mm->cgeom_solimp[g1][k] + (1 - mix) * mm->cgeom_solimp[g2][k];
-      mu = fmax(mm->cgeom_friction[g1][0], mm->cgeom_friction[g2][0]);
-    }
-    d->pair_mu[p] = (float)mu;
-    kb_of(solref, solimp, h, &d->pair_k[p], &d->pair_b[p]);
-    clamp_solimp(solimp, d->pair_solimp[p]);
-    d->pair_margin[p] = (float)(fmax(mm->cgeom_margin[g1], mm->cgeom_margin[g2]) - fmax(mm->cgeom_gap[g1], mm->cgeom_gap[g2]));
-    d->pair_tran[p] = (float)(mm->body_invweight0[mm->cgeom_bodyid[g1]][0] + mm->body_invweight0[mm->cgeom_bodyid[g2]][0]);
-    {  // column support of this pair's contact Jacobian (bodies 2..13 = legs of 3 links, 1 = base)
-      auto cls = [](int b) { return b == 0 ? -1 : (b == 1 ? 4 : (b - 2) / 3); };
-      const int c1 = cls(mm->cgeom_bodyid[g1]), c2 = cls(mm->cgeom_bodyid[g2]);
-      int sup;
-      if (c1 < 0) sup = c2;
-      else if (c2 < 0) sup = c1;
-      else if (c1 == c2) sup = c1;
-      else if (c1 == 4) sup = c2;
-      else if (c2 == 4) sup = c1;
-      else sup = 5 | 8 | ((c1 < c2 ? c1 : c2) << 4) | ((c1 < c2 ? c2 : c1) << 6);  // leg-leg: the pair
-      d->pair_sup[p] = sup < 0 ? 5 : sup;  // (5 without bit 3: legs unknown -> dense LDL^T)
-    }
-    d->pair_dm[p][0] = d->body_dofmask[mm->cgeom_bodyid[g1]];
-    d->pair_dm[p][1] = d->body_dofmask[mm->cgeom_bodyid[g2]];
-    {  // flattened narrow-phase record
-      PairRec r;
-      memset(&r, 0, sizeof(r));
-      const int t1 = mm->cgeom_type[g1], t2 = mm->cgeom_type[g2];
-      r.kind = (t1 == PP3_GEOM_PLANE && t2 == PP3_GEOM_SPHERE) ? PK_PLANE_SPHERE
-               : (t1 == PP3_GEOM_SPHERE && t2 == PP3_GEOM_SPHERE) ? PK_SPHERE_SPHERE
-               : (t1 == PP3_GEOM_SPHERE && t2 == PP3_GEOM_BOX) ? PK_SPHERE_BOX : -1;
-      r.s1 = d->cg_slot[g1];
-      r.s2 = r.kind == PK_SPHERE_BOX ? -1 - box_slot[g2] : d->cg_slot[g2];
-      r.r1 = d->cg_size[g1][0];
-      r.r2 = d->cg_size[g2][0];
-      r.margin = d->pair_margin[p];
-      for (int k = 0; k < 3; k++) { r.p1[k] = d->cg_pos[g1][k]; r.p2[k] = d->cg_pos[g2][k]; }
-      const int gf = r.kind == PK_SPHERE_BOX ? g2 : g1;  // plane frame / box frame
-      for (int k = 0; k < 9; k++) r.R[k] = d->cg_wmat[gf][k];
-      if (r.kind == PK_SPHERE_BOX)
-        for (int k = 0; k < 3; k++) r.half[k] = d->cg_size[g2][k];
-      const float* rf = reinterpret_cast<const float*>(&r);
-      float* g = reinterpret_cast<float*>(reinterpret_cast<char*>(&d->pair_rec) + pair_tab_byte((unsigned)p));
-      for (int k = 0; k < PAIR_REC / 4; k++)
-        for (int c = 0; c < 4; c++) g[128 * k + c] = rf[4 * k + c];
-    }
-    {  // contact-side record
-      PairCon& q = d->pair_con[p];
-      memset(&q, 0, sizeof(q));
-      q.sup = d->pair_sup[p];
-      q.dm[0] = d->pair_dm[p][0];
-      q.dm[1] = d->pair_dm[p][1];
-      q.mu = d->pair_mu[p];
-      q.tran = d->pair_tran[p];
-      q.margin = d->pair_margin[p];
-      q.b = d->pair_b[p];
-      q.k = d->pair_k[p];
-      for (int k = 0; k < 5; k++) q.solimp[k] = d->pair_solimp[p][k];
-      // its first word group (sup, dm, mu) rides with the pair record: PairTab's seventh group
-      memcpy(reinterpret_cast<char*>(&d->pair_rec) + pair_tab_byte((unsigned)p) + 512 * (PAIR_GROUPS - 1), &q, 16);
-    }
-    if (mm->cgeom_margin[g1] != 0 || mm->cgeom_margin[g2] != 0) return set_err(PP3_ERR_MODEL, "nonzero geom margins unsupported");
-  }
-  {  // sphere-box cull tables (DevModel::cull_on)
-    d->cull_on = 0;
-    d->cull_reach = 0.0f;
-    memset(d->pair_box4, 0xFF, sizeof(d->pair_box4));
-    memset(d->box_tab, 0, sizeof(d->box_tab));
-    bool ok = d->nbox >= 1 && d->nbox <= 32 && d->npair > 32 && d->npair <= 32 * 5 && mm->body_parentid[1] == 0;
-    const char* off = getenv("PP3_NO_CULL");  // tests only: every pair through the narrow phase
-    if (off && off[0] == '1') ok = false;
-    double reach = 0.0, margin = 0.0;
-    for (int sl = 0; ok && sl < d->nrobot_geom; sl++) {  // chain of link offsets from body 1's origin
-      const int g = d->robot_geom[sl];
-      const double* gp = mm->cgeom_pos[g];
-      double dist = sqrt(gp[0] * gp[0] + gp[1] * gp[1] + gp[2] * gp[2]);
-      int b = mm->cgeom_bodyid[g];
-      for (; b > 1; b = mm->body_parentid[b]) {
-        const double* bp = mm->body_pos[b];
-        dist += sqrt(bp[0] * bp[0] + bp[1] * bp[1] + bp[2] * bp[2]);
-      }
-      if (b != 1) ok = false;
-      reach = fmax(reach, dist + mm->cgeom_size[g][0]);
-    }
-    for (int p = 0; ok && p < d->npair; p++) {
-      const int g1 = mm->pair_g1[p], g2 = mm->pair_g2[p];
-      const bool sb = mm->cgeom_type[g1] == PP3_GEOM_SPHERE && mm->cgeom_type[g2] == PP3_GEOM_BOX && box_slot[g2] >= 0;
-      if (sb) margin = fmax(margin, (double)d->pair_margin[p]);
-      if (p >= 32 && sb) {
-        const int k = p / 32 - 1, ln = p % 32;
-        d->pair_box4[ln] = (d->pair_box4[ln] & ~(0xFFu << (8 * k))) | ((uint32_t)box_slot[g2] << (8 * k));
-      }
-    }
-    for (int g = 0; ok && g < mm->ncgeom; g++) {
-      if (box_slot[g] < 0) continue;
-      TerrainRec& t = d->box_tab[box_slot[g]];
-      for (int k = 0; k < 3; k++) { t.p[k] = d->cg_pos[g][k]; t.half[k] = d->cg_size[g][k]; }
-      for (int k = 0; k < 9; k++) t.R[k] = d->cg_wmat[g][k];
-    }
-    if (ok) {
-      d->cull_reach = (float)(reach + margin + 0.01);
-      d->cull_on = 1;
-    }
-  }
-  d->nsite = mm->nsite;
-  for (int s = 0; s < mm->nsite; s++) {
-    d->site_body[s] = mm->site_bodyid[s];
-    for (int k = 0; k < 3; k++) d->site_pos[s][k] = (float)mm->site_pos[s][k];
-    for (int k = 0; k < 4; k++) d->site_quat[s][k] = (float)mm->site_quat[s][k];
-  }
-  if (mm->nsensor < 0 || mm->nsensor > PP3_MAX_SENSOR || mm->nsensordata > PP3_MAX_SENSORDATA)
-    return set_err(PP3_ERR_MODEL, "too many sensors");
-  d->nsensor = mm->nsensor;
-  d->nsensordata = mm->nsensordata;
-  for (int i = 0; i < mm->nsensor; i++) {
-    d->sensor_type[i] = mm->sensor_type[i];
-    d->sensor_objid[i] = mm->sensor_objid[i];
-    d->sensor_adr[i] = mm->sensor_adr[i];
-    d->sensor_cutoff[i] = (float)mm->sensor_cutoff[i];
-    if (mm->sensor_objid[i] < 0 || mm->sensor_objid[i] >= mm->nsite) return set_err(PP3_ERR_MODEL, "sensor site id");
-  }
-  for (int b = 0; b < NB; b++) {
-    d->body_parent[b] = mm->body_parentid[b];
-    d->body_dofadr[b] = mm->body_dofadr[b];
-    d->body_dofnum[b] = mm->body_dofnum[b];
-  }
-  for (int i = 0; i < mm->nsensor; i++) {  // the pipeline record's sensor lane records (fill_lane_records)
-    int depth = 0;
-    for (int bb = mm->site_bodyid[mm->sensor_objid[i]]; bb > 0; bb = mm->body_parentid[bb]) depth++;
-    if (depth > LS_MAXCH) return set_err(PP3_ERR_MODEL, "sensor site body deeper than 4 levels");
-  }
-  for (int a = 0; a < NU; a++) {
-    int j = mm->actuator_trnid[a];
-    d->act_dof[a] = mm->jnt_dofadr[j];
-    d->act_qadr[a] = mm->jnt_qposadr[j];
-    if (mm->jnt_dofadr[j] != 6 + a) return set_err(PP3_ERR_MODEL, "actuator i must drive hinge dof 6+i");
-    d->act_biastype[a] = mm->actuator_biastype[a];
-    d->act_forcelimited[a] = mm->actuator_forcelimited[a];
-    d->act_ctrllimited[a] = mm->actuator_ctrllimited[a];
-    d->act_gear[a] = (float)mm->actuator_gear[a];
-    d->act_gain[a] = (float)mm->actuator_gainprm[a][0];
-    for (int k = 0; k < 3; k++) d->act_bias[a][k] = (float)mm->actuator_biasprm[a][k];
-    for (int k = 0; k < 2; k++) {
-      d->act_frange[a][k] = (float)mm->actuator_forcerange[a][k];
-      d->act_crange[a][k] = (float)mm->actuator_ctrlrange[a][k];
-    }
-  }
-  // environment
-  d->n_frames = c->n_frames;
-  d->H = c->obs_history;
-  d->La = c->latency_len;
-  d->Li = c->imu_latency_len;
-  d->use_imu = c->use_imu;
-  d->resample_step = c->resample_velocity_step;
-  d->term_step = c->early_termination_step_threshold;
-  d->torso_body = c->torso_body;
-  if (c->torso_body < 1 || c->torso_body >= NB) return set_err(PP3_ERR_ARG, "torso body id out of range");
-  for (int f = 0; f < 4; f++) {
-    d->feet_site[f] = c->feet_site[f];
-    d->lower_leg_body[f] = c->lower_leg_body[f];
-    if (c->feet_site[f] < 0 || c->feet_site[f] >= mm->nsite) return set_err(PP3_ERR_ARG, "foot site not found");
-    if (c->lower_leg_body[f] < 1 || c->lower_leg_body[f] >= NB) return set_err(PP3_ERR_ARG, "lower-leg body id out of range");
-  }
-  if (c->n_upper_leg_geoms < 0 || c->n_upper_leg_geoms > 16) return set_err(PP3_ERR_ARG, "n_upper_leg_geoms must be 0..16");
-  if (c->n_torso_geoms < 0 || c->n_torso_geoms > 8) return set_err(PP3_ERR_ARG, "n_torso_geoms must be 0..8");
-  d->n_knee_geoms = c->n_upper_leg_geoms;
-  for (int i = 0; i < c->n_upper_leg_geoms && i < 16; i++) d->knee_geoms[i] = c->upper_leg_geoms[i];
-  d->n_torso_geoms = c->n_torso_geoms;
-  for (int i = 0; i < c->n_torso_geoms && i < 8; i++) d->torso_geoms[i] = c->torso_geoms[i];
-  d->partitionable = c->rng_partitionable;
-  d->imu_off = PP3_S_ACT_BUF + 12 * c->latency_len;
-  d->stride = d->imu_off + 6 * c->imu_latency_len;
-  for (int i = 0; i < PP3_MAX_LAG; i++) {
-    d->lat_dist[i] = (float)c->latency_dist[i];
-    d->imu_lat_dist[i] = (float)c->imu_latency_dist[i];
-  }
-  d->action_scale = (float)c->action_scale;
-  for (int j = 0; j < NU; j++) {
-    d->default_pose[j] = (float)c->default_pose[j];
-    d->jlo[j] = (float)c->joint_lower[j];
-    d->jhi[j] = (float)c->joint_upper[j];
-  }
-  for (int k = 0; k < 4; k++) d->des_abd[k] = (float)c->desired_abduction[k];
-  for (int k = 0; k < 3; k++) {
-    d->start_lo[k] = (float)c->start_pos_min[k];
-    d->start_hi[k] = (float)c->start_pos_max[k];
-    d->des_z[k] = (float)c->desired_world_z[k];
-  }
-  for (int k = 0; k < 2; k++) {
-    d->cmd_x[k] = (float)c->lin_vel_x_range[k];
-    d->cmd_y[k] = (float)c->lin_vel_y_range[k];
-    d->cmd_w[k] = (float)c->ang_vel_range[k];
-  }
-  d->zero_cmd_p = (float)c->zero_command_probability;
-  d->stand_thr = (float)c->stand_still_command_threshold;
-  d->max_pitch = (float)c->max_pitch_command;
-  d->max_roll = (float)c->max_roll_command;
-  d->n_ang = (float)c->ang_vel_noise;
-  d->n_grav = (float)c->gravity_noise;
-  d->n_motor = (float)c->motor_angle_noise;
-  d->n_act = (float)c->last_action_noise;
-  d->kick_vel = (float)c->kick_vel;
-  d->kick_p = (float)c->kick_probability;
-  d->term_z = (float)c->terminal_body_z;
-  d->cos_term_angle = (float)cos(c->terminal_body_angle);
-  d->foot_radius = (float)c->foot_radius;
-  d->env_dt = (float)c->env_dt;
-  d->dt = (float)c->dt;
-  for (int k = 0; k < PP3_NREWARD; k++) d->scales[k] = (float)c->reward_scales[k];
-  d->sigma = (float)c->tracking_sigma;
-  d->pi_f = 3.14159265358979323846f;
-  fill_lane_records(d);
-  return PP3_OK;
-}
+bool diag_build() { return PP3_DIAG_BUILD; }
+static_assert(model_limits::HMAX == HMAX && model_limits::NROBOT_GEOM == NROBOT_GEOM, "build_devmodel's limits are the kernels'");
 
 // The step launches of env e take the Caps<2, 2> instantiations (contact cap 8 only: the shipped
 // model's shapes) when its history and both latency rows fit them, the ABI-limit ones otherwise.
 static bool small_caps(const pp3_env_t* e) { return e->nc == 8 && e->H <= CapsSmall::H && e->La <= CapsSmall::LAG && e->Li <= CapsSmall::LAG; }
 
-// launch env_step_kernel<8, FUSED, NWV, CULL, SAMPLE> with the caps of env e
-template <bool FUSED, int NWV, bool CULL, bool SAMPLE, class Args>
-static void launch_nc8(const pp3_env_t* e, dim3 grid, dim3 block, hipStream_t st, const Args& a) {
-  if (small_caps(e)) hipLaunchKernelGGL((env_step_kernel<8, FUSED, NWV, CULL, SAMPLE, CapsSmall>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((env_step_kernel<8, FUSED, NWV, CULL, SAMPLE>), grid, block, 0, st, a);
+// The one place that names env_step_kernel<...>.  The caller knows FUSED, NWV (waves per workgroup:
+// 1, or pp3pol::NWAVE for the policy rollouts), SAMPLE and the argument record that goes with them;
+// the env decides the contact cap, the cull and the caps.  20 instantiations: contact cap 16 only
+// with NWV = 1 and CapsMax (the policy rollouts' fused launch needs policy_rollout_fused(e), so cap
+// 8), CapsSmall only with cap 8 (small_caps).
+template <bool FUSED, int NWV, bool SAMPLE, class Args>
+static void launch_step_kernel(const pp3_env_t* e, hipStream_t st, const Args& a) {
+  const dim3 grid(NWV == 1 ? (e->N + 1) / 2 : (e->N + pp3pol::TILE - 1) / pp3pol::TILE), block(WAVE * NWV);
+  const auto launch = [&](auto nc, auto caps) {
+    constexpr int NC = decltype(nc)::value;
+    using CAPS = decltype(caps);
+    if (e->cull) hipLaunchKernelGGL((env_step_kernel<NC, FUSED, NWV, true, SAMPLE, CAPS>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((env_step_kernel<NC, FUSED, NWV, false, SAMPLE, CAPS>), grid, block, 0, st, a);
+  };
+  if (small_caps(e)) launch(std::integral_constant<int, 8>(), CapsSmall());
+  else if (e->nc == 8) launch(std::integral_constant<int, 8>(), CapsMax());
+  else if constexpr (NWV == 1) launch(std::integral_constant<int, 16>(), CapsMax());
+}
+
+// The StepArgs of env e as far as its handle decides them.  The callers set what differs: the
+// actions and their stride, nsteps / repeat / phase, the trajectory rows.
+static StepArgs step_args(const pp3_env_t* e) {
+  StepArgs a = {};
+  a.m = e->dmodel;
+  a.state = e->state;
+  a.obs_in = e->obs;  // in place: each half-wave loads its env's history before storing it
+  a.obs_out = e->obs;
+  a.reward = e->reward;
+  a.done = e->done;
+  a.metrics = e->metrics;
+  a.dr = e->dr_on ? e->dr : nullptr;
+  a.pipe = e->pipe_on ? e->pipe : nullptr;
+  a.episode = e->episode_length > 0 ? e->episode : nullptr;
+  a.first_state = e->first_state;
+  a.first_obs = e->first_obs;
+  a.episode_length = e->episode_length;
+  a.N = e->N;
+  return a;
+}
+
+// A rollout's trajectory buffers (each optional), and their rows of step t
+struct TrajRows {
+  float *reward, *done, *obs, *trunc;  // [nsteps][N], [nsteps][N], [nsteps][N][36H], [nsteps][N]
+};
+static TrajRows traj_rows_at(const pp3_env_t* e, const TrajRows& r, size_t t) {
+  const size_t n = (size_t)e->N, on = n * PP3_OBS_DIM * e->H;
+  return {r.reward ? r.reward + t * n : nullptr, r.done ? r.done + t * n : nullptr, r.obs ? r.obs + t * on : nullptr,
+          r.trunc ? r.trunc + t * n : nullptr};
 }
 
 extern "C" {
-
-int pp3_abi_version(void) { return PP3_ABI_VERSION; }
 
 size_t pp3_struct_size(int which) {
   if (which == 0) return sizeof(pp3_model_t);
@@ -4127,101 +3626,6 @@ size_t pp3_struct_size(int which) {
   if (which == 4) return sizeof(Shared<16>);
   return 0;
 }
-
-const char* pp3_last_error(void) { return g_err.c_str(); }
-
-int pp3_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-static int alloc_env_buffers(pp3_env* e, const DevModel& hm);
-
-int pp3_create(const pp3_model_t* model, const pp3_env_config_t* cfg, int32_t num_envs, int32_t device, pp3_env_t** out) {
-  if (!model || !cfg || !out || num_envs < 1) return set_err(PP3_ERR_ARG, "bad arguments to pp3_create");
-  if (PP3_DIAG_BUILD) {  // pp3_diag.h: a diagnostic library is never the product
-    const char* ok = getenv("PP3_ALLOW_DIAG_BUILD");
-    if (!ok || strcmp(ok, "1") != 0)
-      return set_err(PP3_ERR_ARG, "pp3_create: this library is a diagnostic build (PP3_PHASE_PROF / PP3_DEBUG); "
-                                  "set PP3_ALLOW_DIAG_BUILD=1 to use it for diagnostics");
-  }
-  DevModel hm;
-  int rc = build_devmodel(model, cfg, &hm);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(device));
-  pp3_env* e = new pp3_env();
-  memset(e, 0, sizeof(*e));
-  e->action_repeat = 1;
-  e->device = device;
-  e->N = num_envs;
-  e->stride = hm.stride;
-  e->H = hm.H;
-  e->La = hm.La;
-  e->Li = hm.Li;
-  e->partitionable = hm.partitionable;
-  e->nbox = hm.nbox;
-  e->cull = hm.cull_on;
-  {
-    // contact cap: 8 deepest per env by default, flat or with obstacle boxes (the reference's
-    // MJX keeps max_contact_points = 5, test_pupper_model.xml:227-230); 16 on request
-    e->nc = cfg->ncon_max > 0 ? cfg->ncon_max : 8;
-    if (e->nc != 8 && e->nc != 16) {
-      delete e;
-      return set_err(PP3_ERR_ARG, "ncon_max must be 0 (auto), 8 or 16");
-    }
-  }
-  rc = alloc_env_buffers(e, hm);
-  if (rc) {
-    pp3_destroy(e);  // frees what was allocated (hipFree(nullptr) is a no-op)
-    return rc;
-  }
-  *out = e;
-  return PP3_OK;
-}
-
-// device buffers of a new handle (pp3_create); on failure the caller destroys the handle
-static int alloc_env_buffers(pp3_env* e, const DevModel& hm) {
-  const size_t N = (size_t)e->N;
-  HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  HIPCHK(hipMalloc(&e->dmodel, sizeof(DevModel)));
-  HIPCHK(hipMemcpy(e->dmodel, &hm, sizeof(DevModel), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&e->state, N * e->stride * sizeof(float)));
-  HIPCHK(hipMalloc(&e->obs, N * PP3_OBS_DIM * e->H * sizeof(float)));
-  HIPCHK(hipMalloc(&e->reward, N * sizeof(float)));
-  HIPCHK(hipMalloc(&e->done, N * sizeof(float)));
-  HIPCHK(hipMalloc(&e->metrics, N * PP3_NMETRIC * sizeof(float)));
-  HIPCHK(hipMalloc(&e->dr, N * PP3_NDR * sizeof(float)));
-  HIPCHK(hipMalloc(&e->pipe, N * PP3_PIPE_STRIDE * sizeof(float)));
-  HIPCHK(hipMalloc(&e->action, N * PP3_NU * sizeof(float)));
-  HIPCHK(hipMemset(e->state, 0, N * e->stride * sizeof(float)));
-  HIPCHK(hipMemset(e->obs, 0, N * PP3_OBS_DIM * e->H * sizeof(float)));
-  HIPCHK(hipMemset(e->pipe, 0, N * PP3_PIPE_STRIDE * sizeof(float)));
-  HIPCHK(hipMemset(e->action, 0, N * PP3_NU * sizeof(float)));
-  HIPCHK(hipEventCreate(&e->ev0));
-  HIPCHK(hipEventCreate(&e->ev1));
-  return PP3_OK;
-}
-
-int pp3_destroy(pp3_env_t* e) {
-  if (!e) return PP3_OK;
-  (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  void* bufs[] = {e->dmodel, e->state, e->obs, e->reward, e->done, e->metrics, e->dr, e->pipe, e->action,
-                  e->episode, e->first_state, e->first_obs, e->terrain};
-  for (void* b : bufs) (void)hipFree(b);
-  if (e->ev0) (void)hipEventDestroy(e->ev0);
-  if (e->ev1) (void)hipEventDestroy(e->ev1);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
-  return PP3_OK;
-}
-
-int32_t pp3_num_envs(const pp3_env_t* e) { return e ? e->N : 0; }
-int32_t pp3_state_stride(const pp3_env_t* e) { return e ? e->stride : 0; }
-int32_t pp3_env_device(const pp3_env_t* e) { return e ? e->device : -1; }
-
-static hipStream_t stream_of(pp3_env_t* e, void* s) { return s ? (hipStream_t)s : e->stream; }
 
 int pp3_reset(pp3_env_t* e, const uint32_t* keys_dev, const uint8_t* mask_dev, void* stream) {
   if (!e || !keys_dev) return set_err(PP3_ERR_ARG, "pp3_reset: null argument");
@@ -4272,63 +3676,35 @@ __global__ void trunc_row_kernel(const float* __restrict__ episode, float* __res
   if (i < n) out[i] = episode ? episode[(size_t)i * PP3_EP_STRIDE + PP3_EP_TRUNCATION] : 0.0f;
 }
 
-static int launch_steps(pp3_env_t* e, const float* actions_dev, int64_t action_stride, int32_t nsteps,
-                        float* traj_reward, float* traj_done, float* traj_obs, float* traj_trunc, bool fused,
-                        void* stream) {
+// auto-reset mode's action_repeat: launches per wrapper step (1 otherwise)
+static int launch_repeat(const pp3_env_t* e) { return e->episode_length > 0 && e->action_repeat > 1 ? e->action_repeat : 1; }
+
+static int launch_steps(pp3_env_t* e, const float* actions_dev, int64_t action_stride, int32_t nsteps, const TrajRows& traj,
+                        bool fused, void* stream) {
   HIPCHK(hipSetDevice(e->device));
-  StepArgs a;
-  a.m = e->dmodel;
-  a.state = e->state;
-  a.obs_in = e->obs;  // in place: each half-wave loads its env's history before storing it
-  a.obs_out = e->obs;
-  a.actions = actions_dev;
-  a.reward = e->reward;
-  a.done = e->done;
-  a.metrics = e->metrics;
-  a.dr = e->dr_on ? e->dr : nullptr;
-  a.pipe = e->pipe_on ? e->pipe : nullptr;
-  a.episode = e->episode_length > 0 ? e->episode : nullptr;
-  a.first_state = e->first_state;
-  a.first_obs = e->first_obs;
-  a.episode_length = e->episode_length;
-  a.N = e->N;
-  a.repeat = e->episode_length > 0 && e->action_repeat > 1 ? e->action_repeat : 1;
+  StepArgs a = step_args(e);
+  a.repeat = launch_repeat(e);
   a.act_stride = action_stride;
   // a one-step rollout takes the single-step kernel: a fused launch of one step measured 7 % slower
   // than it (the fused kernel only pays off across steps)
   if (nsteps == 1) fused = false;
   const bool one_launch = fused && a.repeat == 1;
   a.nsteps = one_launch ? nsteps : 1;
-  const dim3 grid((e->N + 1) / 2), block(WAVE);
   const hipStream_t st = stream_of(e, stream);
-  const size_t on = (size_t)e->N * PP3_OBS_DIM * e->H;
-  for (int t = 0; t < (one_launch ? 1 : nsteps); t++) {
-    a.actions = actions_dev + (one_launch ? 0 : (size_t)t * (size_t)action_stride);
-    a.traj_reward = traj_reward ? traj_reward + (one_launch ? 0 : (size_t)t * e->N) : nullptr;
-    a.traj_done = traj_done ? traj_done + (one_launch ? 0 : (size_t)t * e->N) : nullptr;
-    a.traj_obs = traj_obs ? traj_obs + (one_launch ? 0 : (size_t)t * on) : nullptr;
-    float* const trunc_row = traj_trunc ? traj_trunc + (one_launch ? 0 : (size_t)t * e->N) : nullptr;
-    a.traj_trunc = fused ? trunc_row : nullptr;
+  for (int t = 0; t < (one_launch ? 1 : nsteps); t++) {  // (one launch: t = 0, the buffers' first rows)
+    const TrajRows row = traj_rows_at(e, traj, t);
+    a.actions = actions_dev + (size_t)t * (size_t)action_stride;
+    a.traj_reward = row.reward;
+    a.traj_done = row.done;
+    a.traj_obs = row.obs;
+    a.traj_trunc = fused ? row.trunc : nullptr;
     for (a.phase = 0; a.phase < a.repeat; a.phase++) {  // action_repeat: the same action, k launches
-      if (e->cull) {
-        if (fused) {
-          if (e->nc == 8) launch_nc8<true, 1, true, false>(e, grid, block, st, a);
-          else hipLaunchKernelGGL((env_step_kernel<16, true, 1, true>), grid, block, 0, st, a);
-        } else {
-          if (e->nc == 8) launch_nc8<false, 1, true, false>(e, grid, block, st, a);
-          else hipLaunchKernelGGL((env_step_kernel<16, false, 1, true>), grid, block, 0, st, a);
-        }
-      } else if (fused) {
-        if (e->nc == 8) launch_nc8<true, 1, false, false>(e, grid, block, st, a);
-        else hipLaunchKernelGGL((env_step_kernel<16, true>), grid, block, 0, st, a);
-      } else {
-        if (e->nc == 8) launch_nc8<false, 1, false, false>(e, grid, block, st, a);
-        else hipLaunchKernelGGL((env_step_kernel<16, false>), grid, block, 0, st, a);
-      }
+      if (fused) launch_step_kernel<true, 1, false>(e, st, a);
+      else launch_step_kernel<false, 1, false>(e, st, a);
       HIPCHK(hipGetLastError());
     }
-    if (trunc_row && !fused) {  // after the wrapper step's last repeat
-      hipLaunchKernelGGL(trunc_row_kernel, dim3((e->N + 255) / 256), dim3(256), 0, st, a.episode, trunc_row, e->N);
+    if (row.trunc && !fused) {  // after the wrapper step's last repeat
+      hipLaunchKernelGGL(trunc_row_kernel, dim3((e->N + 255) / 256), dim3(256), 0, st, a.episode, row.trunc, e->N);
       HIPCHK(hipGetLastError());
     }
   }
@@ -4337,7 +3713,7 @@ static int launch_steps(pp3_env_t* e, const float* actions_dev, int64_t action_s
 
 int pp3_step(pp3_env_t* e, const float* actions_dev, void* stream) {
   if (!e || !actions_dev) return set_err(PP3_ERR_ARG, "pp3_step: null argument");
-  return launch_steps(e, actions_dev, 0, 1, nullptr, nullptr, nullptr, nullptr, false, stream);
+  return launch_steps(e, actions_dev, 0, 1, TrajRows{}, false, stream);
 }
 
 int pp3_rollout(pp3_env_t* e, const float* actions_dev, int64_t action_stride, int32_t nsteps, float* reward_dev,
@@ -4346,7 +3722,8 @@ int pp3_rollout(pp3_env_t* e, const float* actions_dev, int64_t action_stride, i
   if (nsteps < 1) return set_err(PP3_ERR_ARG, "pp3_rollout: nsteps must be >= 1");
   if (action_stride < 0) return set_err(PP3_ERR_ARG, "pp3_rollout: negative action_stride");
   if (trunc_over(e, nsteps)) return set_err(PP3_ERR_ARG, "pp3_rollout: " + trunc_over_msg(e, nsteps));
-  return launch_steps(e, actions_dev, action_stride, nsteps, reward_dev, done_dev, obs_dev, e->traj_trunc, true, stream);
+  return launch_steps(e, actions_dev, action_stride, nsteps, TrajRows{reward_dev, done_dev, obs_dev, e->traj_trunc}, true,
+                      stream);
 }
 
 // Which path pp3_rollout_policy takes on this env: ONE fused launch (env_step_kernel<8, true, 8>)
@@ -4358,13 +3735,11 @@ static bool policy_rollout_fused(const pp3_env_t* e) {
   (void)e;
   return false;
 #else
-  const int repeat = e->episode_length > 0 && e->action_repeat > 1 ? e->action_repeat : 1;
-  return e->nc == 8 && repeat == 1 && !g_policy_unfused;
+  return e->nc == 8 && launch_repeat(e) == 1 && !g_policy_unfused;
 #endif
 }
 
 int32_t pp3_rollout_policy_fused(const pp3_env_t* e) { return e ? (policy_rollout_fused(e) ? 1 : 0) : -1; }
-int32_t pp3_narrow_cull(const pp3_env_t* e) { return e ? (e->cull ? 1 : 0) : -1; }
 // (every launch kind decides by small_caps alone today: a fused rollout, a single step, the policy
 // rollouts' fused kernel and their per-step launches)
 int32_t pp3_diag_step_variant(const pp3_env_t* e, int32_t fused, int32_t policy) {
@@ -4374,53 +3749,51 @@ int32_t pp3_diag_step_variant(const pp3_env_t* e, int32_t fused, int32_t policy)
   return small_caps(e) ? (CapsSmall::H << 8 | CapsSmall::LAG) : (CapsMax::H << 8 | CapsMax::LAG);
 }
 
+// What the two policy rollouts `fn` check alike once their own arguments are in order
+static int policy_rollout_check(const std::string& fn, const pp3_env_t* e, pp3_policy_t* policy, int nsteps) {
+  if (pp3_policy_device(policy) != e->device) return set_err(PP3_ERR_ARG, fn + ": policy and env on different devices");
+  if (pp3_policy_net(policy)->in_dim != PP3_OBS_DIM * e->H)
+    return set_err(PP3_ERR_ARG, fn + ": the policy's input width must equal the observation size 36 * observation_history");
+  if (trunc_over(e, nsteps)) return set_err(PP3_ERR_ARG, fn + ": " + trunc_over_msg(e, nsteps));
+  return PP3_OK;
+}
+
+#ifndef PP3_PHASE_PROF
+// The argument record of the policy rollouts' ONE launch for the K steps: 8-wave workgroups of 16
+// envs run the MLP (mlp_tile, the code of pp3_policy_act) on their envs' observations before each
+// step, then each wave steps its two envs (env_step_kernel<8, true, 8>)
+static PolicyStepArgs policy_step_args(const pp3_env_t* e, pp3_policy_t* policy, int nsteps, float* actions_dev,
+                                       const TrajRows& traj) {
+  PolicyStepArgs pa;
+  StepArgs& a = pa.s;
+  a = step_args(e);
+  a.actions = actions_dev;
+  a.repeat = 1;
+  a.phase = 0;
+  a.nsteps = nsteps;
+  a.act_stride = (int64_t)e->N * NU;
+  a.traj_reward = traj.reward;
+  a.traj_done = traj.done;
+  a.traj_obs = traj.obs;
+  a.traj_trunc = traj.trunc;
+  pa.act = actions_dev;
+  pa.net = *pp3_policy_net(policy);
+  return pa;
+}
+#endif
+
 int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float* actions_dev, float* reward_dev,
                        float* done_dev, float* obs_dev, void* stream) {
   if (!e || !policy || !actions_dev) return set_err(PP3_ERR_ARG, "pp3_rollout_policy: null argument");
   if (nsteps < 1) return set_err(PP3_ERR_ARG, "pp3_rollout_policy: nsteps must be >= 1");
   if (pp3_policy_out_dim(policy) != NU) return set_err(PP3_ERR_ARG, "pp3_rollout_policy: the policy must have 12 outputs");
-  if (pp3_policy_device(policy) != e->device) return set_err(PP3_ERR_ARG, "pp3_rollout_policy: policy and env on different devices");
-  if (pp3_policy_net(policy)->in_dim != PP3_OBS_DIM * e->H)
-    return set_err(PP3_ERR_ARG, "pp3_rollout_policy: the policy's input width must equal the observation size 36 * observation_history");
-  if (trunc_over(e, nsteps)) return set_err(PP3_ERR_ARG, "pp3_rollout_policy: " + trunc_over_msg(e, nsteps));
-  const size_t on = (size_t)e->N * PP3_OBS_DIM * e->H;
+  if (int rc = policy_rollout_check("pp3_rollout_policy", e, policy, nsteps)) return rc;
+  const TrajRows traj{reward_dev, done_dev, obs_dev, e->traj_trunc};
   const hipStream_t st = stream_of(e, stream);
 #ifndef PP3_PHASE_PROF
   if (policy_rollout_fused(e)) {
-    // ONE launch for the K steps: 8-wave workgroups of 16 envs run the MLP (mlp_tile, the code of
-    // pp3_policy_act) on their envs' observations before each step, then each wave steps its two
-    // envs (env_step_kernel<8, true, 8>)
     HIPCHK(hipSetDevice(e->device));
-    PolicyStepArgs pa;
-    StepArgs& a = pa.s;
-    a.m = e->dmodel;
-    a.state = e->state;
-    a.obs_in = e->obs;
-    a.obs_out = e->obs;
-    a.actions = actions_dev;
-    a.reward = e->reward;
-    a.done = e->done;
-    a.metrics = e->metrics;
-    a.dr = e->dr_on ? e->dr : nullptr;
-    a.pipe = e->pipe_on ? e->pipe : nullptr;
-    a.episode = e->episode_length > 0 ? e->episode : nullptr;
-    a.first_state = e->first_state;
-    a.first_obs = e->first_obs;
-    a.episode_length = e->episode_length;
-    a.N = e->N;
-    a.repeat = 1;
-    a.phase = 0;
-    a.nsteps = nsteps;
-    a.act_stride = (int64_t)e->N * NU;
-    a.traj_reward = reward_dev;
-    a.traj_done = done_dev;
-    a.traj_obs = obs_dev;
-    a.traj_trunc = e->traj_trunc;
-    pa.act = actions_dev;
-    pa.net = *pp3_policy_net(policy);
-    const dim3 grid((e->N + pp3pol::TILE - 1) / pp3pol::TILE), block(WAVE * pp3pol::NWAVE);
-    if (e->cull) launch_nc8<true, pp3pol::NWAVE, true, false>(e, grid, block, st, pa);
-    else launch_nc8<true, pp3pol::NWAVE, false, false>(e, grid, block, st, pa);
+    launch_step_kernel<true, pp3pol::NWAVE, false>(e, st, policy_step_args(e, policy, nsteps, actions_dev, traj));
     HIPCHK(hipGetLastError());
     return PP3_OK;
   }
@@ -4432,55 +3805,11 @@ int pp3_rollout_policy(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float
     float* act = actions_dev + (size_t)t * e->N * NU;
     if (pp3_policy_act(policy, e->obs, PP3_OBS_DIM * e->H, e->N, act, NU, (void*)st) != PP3_OK)
       return set_err(PP3_ERR_ARG, std::string("pp3_rollout_policy: ") + pp3_policy_last_error());
-    const int rc = launch_steps(e, act, 0, 1, reward_dev ? reward_dev + (size_t)t * e->N : nullptr,
-                                done_dev ? done_dev + (size_t)t * e->N : nullptr, obs_dev ? obs_dev + (size_t)t * on : nullptr,
-                                e->traj_trunc ? e->traj_trunc + (size_t)t * e->N : nullptr, false, (void*)st);
+    const int rc = launch_steps(e, act, 0, 1, traj_rows_at(e, traj, t), false, (void*)st);
     if (rc) return rc;
   }
   return PP3_OK;
 }
-
-}  // extern "C"
-
-// Host restatement of threefry and split(key)[i] (pp3_mlp.h head_threefry / head_split2 are the
-// device's), for the sampled rollout's key chain:
-// the per-step keys of the unfused path and the returned K_nsteps.
-static void host_threefry(uint32_t k0, uint32_t k1, uint32_t x0, uint32_t x1, uint32_t& y0, uint32_t& y1) {
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  static const int rot[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-  x0 += k0;
-  x1 += k1;
-  for (int i = 0; i < 5; i++) {
-    for (int q = 0; q < 4; q++) {
-      x0 += x1;
-      x1 = (x1 << rot[i & 1][q]) | (x1 >> (32 - rot[i & 1][q]));
-      x1 ^= x0;
-    }
-    x0 += ks[(i + 1) % 3];
-    x1 += ks[(i + 2) % 3] + (uint32_t)(i + 1);
-  }
-  y0 = x0;
-  y1 = x1;
-}
-// jax.random.split(k)[i], i in {0, 1}
-static Key host_split2(Key k, int i, int part) {
-  Key r;
-  uint32_t y0, y1;
-  if (part) {
-    host_threefry(k.a, k.b, 0u, (uint32_t)i, y0, y1);
-    r.a = y0;
-    r.b = y1;
-  } else {  // flat words [y0(0,2), y0(1,3), y1(0,2), y1(1,3)]: key i = words 2i, 2i + 1
-    uint32_t a0, a1, b0, b1;
-    host_threefry(k.a, k.b, 0u, 2u, a0, a1);
-    host_threefry(k.a, k.b, 1u, 3u, b0, b1);
-    r.a = i ? a1 : a0;
-    r.b = i ? b1 : b0;
-  }
-  return r;
-}
-
-extern "C" {
 
 int pp3_rollout_policy_sample(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, const uint32_t* key, uint32_t* key_out,
                               float* actions_dev, float* raw_dev, float* logp_dev, float* reward_dev, float* done_dev,
@@ -4491,208 +3820,50 @@ int pp3_rollout_policy_sample(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps
   float min_std, var_scale;
   if (!pp3_policy_distribution(policy, &min_std, &var_scale))
     return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: the policy has no distribution (pp3_policy_set_distribution)");
-  if (pp3_policy_device(policy) != e->device)
-    return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: policy and env on different devices");
-  if (pp3_policy_net(policy)->in_dim != PP3_OBS_DIM * e->H)
-    return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: the policy's input width must equal the observation size 36 * observation_history");
-  if (trunc_over(e, nsteps)) return set_err(PP3_ERR_ARG, "pp3_rollout_policy_sample: " + trunc_over_msg(e, nsteps));
-  const size_t on = (size_t)e->N * PP3_OBS_DIM * e->H;
+  if (int rc = policy_rollout_check("pp3_rollout_policy_sample", e, policy, nsteps)) return rc;
+  const TrajRows traj{reward_dev, done_dev, obs_dev, e->traj_trunc};
   const hipStream_t st = stream_of(e, stream);
   const int part = e->partitionable;
-  const Key k0{key[0], key[1]};
+  // the unroll's key chain on the host (pp3_env_host.h host_split): K_t -> this step's sampling
+  // key kk[0..1] and K_{t+1} = kk[2..3]; key_out = K_nsteps
+  uint32_t kk[4] = {0, 0, key[0], key[1]};
 #ifndef PP3_PHASE_PROF
   if (policy_rollout_fused(e)) {
     // ONE launch, as pp3_rollout_policy: the workgroup's MLP ends in the head, the key chain
     // advances in the kernel (env_step_kernel<8, true, 8, CULL, true>)
     HIPCHK(hipSetDevice(e->device));
     SamplePolicyStepArgs sa;
-    StepArgs& a = sa.p.s;
-    a.m = e->dmodel;
-    a.state = e->state;
-    a.obs_in = e->obs;
-    a.obs_out = e->obs;
-    a.actions = actions_dev;
-    a.reward = e->reward;
-    a.done = e->done;
-    a.metrics = e->metrics;
-    a.dr = e->dr_on ? e->dr : nullptr;
-    a.pipe = e->pipe_on ? e->pipe : nullptr;
-    a.episode = e->episode_length > 0 ? e->episode : nullptr;
-    a.first_state = e->first_state;
-    a.first_obs = e->first_obs;
-    a.episode_length = e->episode_length;
-    a.N = e->N;
-    a.repeat = 1;
-    a.phase = 0;
-    a.nsteps = nsteps;
-    a.act_stride = (int64_t)e->N * NU;
-    a.traj_reward = reward_dev;
-    a.traj_done = done_dev;
-    a.traj_obs = obs_dev;
-    a.traj_trunc = e->traj_trunc;
-    sa.p.act = actions_dev;
-    sa.p.net = *pp3_policy_net(policy);
+    sa.p = policy_step_args(e, policy, nsteps, actions_dev, traj);
     sa.raw = raw_dev;
     sa.logp = logp_dev;
-    sa.k0 = k0.a;
-    sa.k1 = k0.b;
+    sa.k0 = key[0];
+    sa.k1 = key[1];
     sa.min_std = min_std;
     sa.var_scale = var_scale;
-    const dim3 grid((e->N + pp3pol::TILE - 1) / pp3pol::TILE), block(WAVE * pp3pol::NWAVE);
-    if (e->cull) launch_nc8<true, pp3pol::NWAVE, true, true>(e, grid, block, st, sa);
-    else launch_nc8<true, pp3pol::NWAVE, false, true>(e, grid, block, st, sa);
+    launch_step_kernel<true, pp3pol::NWAVE, true>(e, st, sa);
     HIPCHK(hipGetLastError());
-    Key kt = k0;  // K_nsteps: the chain's `next` halves (host threefry)
-    for (int t = 0; t < nsteps; t++) kt = host_split2(kt, 1, part);
-    key_out[0] = kt.a;
-    key_out[1] = kt.b;
+    for (int t = 0; t < nsteps; t++) host_split(kk[2], kk[3], part, kk);
+    key_out[0] = kk[2];
+    key_out[1] = kk[3];
     return PP3_OK;
   }
 #endif
   // per step: the sample launch with that step's key on the env's obs buffer, then the step launch
-  Key kt = k0;
   for (int t = 0; t < nsteps; t++) {
-    const Key cur = host_split2(kt, 0, part);
-    kt = host_split2(kt, 1, part);
-    const uint32_t kw[2] = {cur.a, cur.b};
+    host_split(kk[2], kk[3], part, kk);
     float* act = actions_dev + (size_t)t * e->N * NU;
-    if (pp3_policy_sample(policy, e->obs, PP3_OBS_DIM * e->H, e->N, kw, part, act, NU,
+    if (pp3_policy_sample(policy, e->obs, PP3_OBS_DIM * e->H, e->N, kk, part, act, NU,
                           raw_dev ? raw_dev + (size_t)t * e->N * NU : nullptr,
                           logp_dev ? logp_dev + (size_t)t * e->N : nullptr, nullptr, (void*)st) != PP3_OK)
       return set_err(PP3_ERR_ARG, std::string("pp3_rollout_policy_sample: ") + pp3_policy_last_error());
-    const int rc = launch_steps(e, act, 0, 1, reward_dev ? reward_dev + (size_t)t * e->N : nullptr,
-                                done_dev ? done_dev + (size_t)t * e->N : nullptr, obs_dev ? obs_dev + (size_t)t * on : nullptr,
-                                e->traj_trunc ? e->traj_trunc + (size_t)t * e->N : nullptr, false, (void*)st);
+    const int rc = launch_steps(e, act, 0, 1, traj_rows_at(e, traj, t), false, (void*)st);
     if (rc) return rc;
   }
-  key_out[0] = kt.a;
-  key_out[1] = kt.b;
+  key_out[0] = kk[2];
+  key_out[1] = kk[3];
   return PP3_OK;
 }
 
-void* pp3_stream(pp3_env_t* e) { return e ? (void*)e->stream : nullptr; }
-
-// completion markers of the host API's asynchronous step (timing disabled: a record is one packet)
-int pp3_event_create(pp3_env_t* e, void** out) {
-  if (!e || !out) return set_err(PP3_ERR_ARG, "pp3_event_create: null argument");
-  HIPCHK(hipSetDevice(e->device));
-  hipEvent_t ev;
-  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  *out = (void*)ev;
-  return PP3_OK;
-}
-int pp3_event_record(pp3_env_t* e, void* ev) {
-  if (!e || !ev) return set_err(PP3_ERR_ARG, "pp3_event_record: null argument");
-  HIPCHK(hipEventRecord((hipEvent_t)ev, e->stream));
-  return PP3_OK;
-}
-int pp3_event_synchronize(void* ev) {
-  if (!ev) return set_err(PP3_ERR_ARG, "pp3_event_synchronize: null event");
-  HIPCHK(hipEventSynchronize((hipEvent_t)ev));
-  return PP3_OK;
-}
-int pp3_event_destroy(void* ev) {
-  if (ev) HIPCHK(hipEventDestroy((hipEvent_t)ev));
-  return PP3_OK;
-}
-
-int pp3_set_auto_reset(pp3_env_t* e, int32_t episode_length) {
-  if (!e) return set_err(PP3_ERR_ARG, "null env");
-  HIPCHK(hipSetDevice(e->device));
-  if (episode_length > 0 && !e->episode) {
-    HIPCHK(hipMalloc(&e->episode, sizeof(float) * (size_t)e->N * PP3_EP_STRIDE));
-    HIPCHK(hipMalloc(&e->first_state, sizeof(float) * (size_t)e->N * PP3_FIRST_STRIDE));
-    HIPCHK(hipMalloc(&e->first_obs, sizeof(float) * (size_t)e->N * PP3_OBS_DIM * e->H));
-    HIPCHK(hipMemsetAsync(e->episode, 0, sizeof(float) * (size_t)e->N * PP3_EP_STRIDE, e->stream));
-    // until the next pp3_reset the current state is the "first" state
-    HIPCHK(hipMemcpy2DAsync(e->first_state, sizeof(float) * PP3_FIRST_STRIDE, e->state, sizeof(float) * e->stride,
-                            sizeof(float) * PP3_FIRST_STRIDE, e->N, hipMemcpyDeviceToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->first_obs, e->obs, sizeof(float) * (size_t)e->N * PP3_OBS_DIM * e->H,
-                          hipMemcpyDeviceToDevice, e->stream));
-  }
-  e->episode_length = episode_length > 0 ? episode_length : 0;
-  if (e->episode_length == 0) e->action_repeat = 1;
-  return PP3_OK;
-}
-
-int pp3_set_truncation_trajectory(pp3_env_t* e, float* trunc_dev, int32_t max_steps) {
-  if (!e) return set_err(PP3_ERR_ARG, "null env");
-  if (trunc_dev && max_steps < 1) return set_err(PP3_ERR_ARG, "pp3_set_truncation_trajectory: max_steps must be >= 1");
-  e->traj_trunc = trunc_dev;
-  e->trunc_steps = trunc_dev ? max_steps : 0;
-  return PP3_OK;
-}
-
-int pp3_set_action_repeat(pp3_env_t* e, int32_t action_repeat) {
-  if (!e) return set_err(PP3_ERR_ARG, "null env");
-  if (action_repeat < 1) return set_err(PP3_ERR_ARG, "action_repeat must be >= 1");
-  if (action_repeat > 1 && e->episode_length <= 0)
-    return set_err(PP3_ERR_ARG, "action_repeat > 1 needs auto-reset mode (pp3_set_auto_reset first)");
-  e->action_repeat = action_repeat;
-  return PP3_OK;
-}
-
-int pp3_set_dr(pp3_env_t* e, const float* dr_dev) {
-  if (!e) return set_err(PP3_ERR_ARG, "null env");
-  HIPCHK(hipSetDevice(e->device));
-  if (!dr_dev) { e->dr_on = 0; return PP3_OK; }
-  HIPCHK(hipMemcpyAsync(e->dr, dr_dev, (size_t)e->N * PP3_NDR * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-  e->dr_on = 1;
-  return PP3_OK;
-}
-
-int32_t pp3_terrain_slots(const pp3_env_t* e) { return e ? e->nbox : 0; }
-
-int pp3_set_terrain(pp3_env_t* e, const float* boxes, int32_t n_boxes) {
-  if (!e) return set_err(PP3_ERR_ARG, "null env");
-  HIPCHK(hipSetDevice(e->device));
-  uint64_t ptr = 0;
-  if (boxes) {
-    if (n_boxes != e->nbox)
-      return set_err(PP3_ERR_ARG, "pp3_set_terrain: n_boxes must equal the model's world box-geom count (" +
-                                      std::to_string(e->nbox) + ")");
-    if (n_boxes == 0) return set_err(PP3_ERR_ARG, "pp3_set_terrain: the model has no box geoms to use as slots");
-    const size_t rows = (size_t)(e->N + 1) / 2 * 2;  // even: the kernel indexes by 2 * block + half
-    std::vector<TerrainRec> rec(rows * n_boxes);
-    memset(rec.data(), 0, rec.size() * sizeof(TerrainRec));
-    for (size_t i = 0; i < rows; i++)
-      for (int b = 0; b < n_boxes; b++) {
-        TerrainRec& r = rec[i * n_boxes + b];
-        if (i >= (size_t)e->N) {  // padding row: absent boxes
-          r.p[2] = -1e4f;
-          continue;
-        }
-        const float* x = boxes + (i * n_boxes + b) * PP3_TERRAIN_BOX;
-        if (!(x[7] > 0 || x[8] > 0 || x[9] > 0)) {  // absent: far below the floor, zero size
-          r.p[2] = -1e4f;
-          r.R[0] = r.R[4] = r.R[8] = 1.0f;
-          continue;
-        }
-        double q[4] = {x[3], x[4], x[5], x[6]};
-        const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        if (!(qn > 0)) return set_err(PP3_ERR_ARG, "pp3_set_terrain: zero quaternion");
-        for (int k = 0; k < 4; k++) q[k] /= qn;
-        double R[9];
-        quat2mat_d(q, R);
-        for (int k = 0; k < 3; k++) { r.p[k] = x[k]; r.half[k] = x[7 + k]; }
-        for (int k = 0; k < 9; k++) r.R[k] = (float)R[k];
-      }
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (!e->terrain) HIPCHK(hipMalloc(&e->terrain, rows * n_boxes * sizeof(TerrainRec)));
-    HIPCHK(hipMemcpy(e->terrain, rec.data(), rec.size() * sizeof(TerrainRec), hipMemcpyHostToDevice));
-    ptr = (uint64_t)(uintptr_t)e->terrain;
-  } else {
-    HIPCHK(hipStreamSynchronize(e->stream));
-  }
-  HIPCHK(hipMemcpy((char*)e->dmodel + offsetof(DevModel, terrain), &ptr, sizeof(ptr), hipMemcpyHostToDevice));
-  return PP3_OK;
-}
-
-int pp3_set_pipeline_output(pp3_env_t* e, int32_t enable) {
-  if (!e) return set_err(PP3_ERR_ARG, "null env");
-  e->pipe_on = enable ? 1 : 0;
-  return PP3_OK;
-}
 
 int pp3_physics_step(pp3_env_t* e, const float* ctrl_dev, int32_t nsteps, void* stream) {
   if (!e || !ctrl_dev || nsteps < 0) return set_err(PP3_ERR_ARG, "pp3_physics_step: bad argument");
@@ -4708,76 +3879,6 @@ int pp3_physics_step(pp3_env_t* e, const float* ctrl_dev, int32_t nsteps, void* 
   if (e->nc == 8) hipLaunchKernelGGL(physics_kernel<8>, dim3((e->N + 1) / 2), dim3(WAVE), 0, stream_of(e, stream), a);
   else hipLaunchKernelGGL(physics_kernel<16>, dim3((e->N + 1) / 2), dim3(WAVE), 0, stream_of(e, stream), a);
   HIPCHK(hipGetLastError());
-  return PP3_OK;
-}
-
-int pp3_field(pp3_env_t* e, int32_t field, void** ptr, int64_t* elems) {
-  if (!e || !ptr) return set_err(PP3_ERR_ARG, "null argument");
-  int64_t n = 0;
-  void* p = nullptr;
-  switch (field) {
-    case PP3_F_STATE: p = e->state; n = e->stride; break;
-    case PP3_F_OBS: p = e->obs; n = (int64_t)PP3_OBS_DIM * e->H; break;
-    case PP3_F_REWARD: p = e->reward; n = 1; break;
-    case PP3_F_DONE: p = e->done; n = 1; break;
-    case PP3_F_METRICS: p = e->metrics; n = PP3_NMETRIC; break;
-    case PP3_F_DR: p = e->dr; n = PP3_NDR; break;
-    case PP3_F_PIPELINE: p = e->pipe; n = PP3_PIPE_STRIDE; break;
-    case PP3_F_ACTION: p = e->action; n = PP3_NU; break;
-    case PP3_F_EPISODE: p = e->episode; n = PP3_EP_STRIDE; break;
-    case PP3_F_FIRST_STATE: p = e->first_state; n = PP3_FIRST_STRIDE; break;
-    case PP3_F_FIRST_OBS: p = e->first_obs; n = (int64_t)PP3_OBS_DIM * e->H; break;
-    default: return set_err(PP3_ERR_ARG, "unknown field");
-  }
-  *ptr = p;
-  if (elems) *elems = n;
-  return PP3_OK;
-}
-
-int pp3_copy_field_to_host(pp3_env_t* e, int32_t field, void* host, size_t bytes) {
-  void* p;
-  int64_t n;
-  int rc = pp3_field(e, field, &p, &n);
-  if (rc) return rc;
-  if (bytes != (size_t)n * e->N * 4) return set_err(PP3_ERR_ARG, "pp3_copy_field_to_host: size mismatch");
-  if (!p) return set_err(PP3_ERR_ARG, "pp3_copy_field_to_host: field not allocated (auto-reset fields need pp3_set_auto_reset)");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost));
-  return PP3_OK;
-}
-
-int pp3_copy_field_from_host(pp3_env_t* e, int32_t field, const void* host, size_t bytes) {
-  void* p;
-  int64_t n;
-  int rc = pp3_field(e, field, &p, &n);
-  if (rc) return rc;
-  if (bytes != (size_t)n * e->N * 4) return set_err(PP3_ERR_ARG, "pp3_copy_field_from_host: size mismatch");
-  if (!p) return set_err(PP3_ERR_ARG, "pp3_copy_field_from_host: field not allocated (auto-reset fields need pp3_set_auto_reset)");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-  if (field == PP3_F_DR) e->dr_on = 1;
-  return PP3_OK;
-}
-
-int pp3_synchronize(pp3_env_t* e) {
-  if (!e) return set_err(PP3_ERR_ARG, "null env");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipDeviceSynchronize());
-  return PP3_OK;
-}
-
-int pp3_copy_field_to_host_async(pp3_env_t* e, int32_t field, void* host, size_t bytes) {
-  void* p;
-  int64_t n;
-  int rc = pp3_field(e, field, &p, &n);
-  if (rc) return rc;
-  if (bytes != (size_t)n * e->N * 4) return set_err(PP3_ERR_ARG, "pp3_copy_field_to_host_async: size mismatch");
-  if (!p) return set_err(PP3_ERR_ARG, "pp3_copy_field_to_host_async: field not allocated");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(host, p, bytes, hipMemcpyDeviceToHost, e->stream));
   return PP3_OK;
 }
 
@@ -4802,51 +3903,6 @@ int pp3_outputs_to_host(pp3_env_t* e, float* host) {
   hipLaunchKernelGGL(outputs_to_host_kernel, dim3(blocks), dim3(256), 0, e->stream, e->obs, e->reward, e->done, nobs,
                      e->N, hdev);
   HIPCHK(hipGetLastError());
-  return PP3_OK;
-}
-
-int pp3_host_device_ptr(void* host, void** dev) {
-  if (!host || !dev) return set_err(PP3_ERR_ARG, "pp3_host_device_ptr: null argument");
-  *dev = nullptr;
-  if (hipHostGetDevicePointer(dev, host, 0) != hipSuccess || !*dev)
-    return set_err(PP3_ERR_ARG, "pp3_host_device_ptr: not page-locked memory from pp3_host_malloc");
-  return PP3_OK;
-}
-
-int pp3_memcpy_h2d_async(void* dst, const void* src, size_t bytes, void* stream) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-  return PP3_OK;
-}
-
-int pp3_host_malloc(size_t bytes, void** out) {
-  if (!out) return set_err(PP3_ERR_ARG, "pp3_host_malloc: null output");
-  HIPCHK(hipHostMalloc(out, bytes, hipHostMallocDefault));
-  return PP3_OK;
-}
-int pp3_host_free(void* p) {
-  HIPCHK(hipHostFree(p));
-  return PP3_OK;
-}
-
-int pp3_device_malloc(int32_t device, size_t bytes, void** out) {
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipMalloc(out, bytes));
-  return PP3_OK;
-}
-int pp3_device_free(void* p) {
-  HIPCHK(hipFree(p));
-  return PP3_OK;
-}
-int pp3_memcpy_h2d(void* dst, const void* src, size_t bytes) {
-  HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-  return PP3_OK;
-}
-int pp3_memcpy_d2h(void* dst, const void* src, size_t bytes) {
-  HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-  return PP3_OK;
-}
-int pp3_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return PP3_OK;
 }
 
@@ -4902,60 +3958,35 @@ int pp3_phase_profile(uint64_t* host_out, int32_t n, int32_t reset) {
 #endif
 }
 
-int pp3_step_timed(pp3_env_t* e, const float* actions_dev, int64_t action_stride, int32_t nsteps,
-                   float* kernel_ms_total) {
-  if (!e || !actions_dev || !kernel_ms_total) return set_err(PP3_ERR_ARG, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  for (int i = 0; i < nsteps; i++) {
-    int rc = pp3_step(e, actions_dev + (size_t)i * (size_t)action_stride, e->stream);
-    if (rc) return rc;
-  }
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipEventSynchronize(e->ev1));
-  HIPCHK(hipEventElapsedTime(kernel_ms_total, e->ev0, e->ev1));
-  return PP3_OK;
-}
-
-int pp3_rollout_timed(pp3_env_t* e, const float* actions_dev, int64_t action_stride, int32_t nsteps,
-                      float* reward_dev, float* done_dev, float* obs_dev, float* kernel_ms_total) {
-  if (!e || !actions_dev || !kernel_ms_total) return set_err(PP3_ERR_ARG, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  const int rc = pp3_rollout(e, actions_dev, action_stride, nsteps, reward_dev, done_dev, obs_dev, e->stream);
-  if (rc) return rc;
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipEventSynchronize(e->ev1));
-  HIPCHK(hipEventElapsedTime(kernel_ms_total, e->ev0, e->ev1));
-  return PP3_OK;
-}
-
-int pp3_rollout_policy_timed(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, float* actions_dev,
-                             float* reward_dev, float* done_dev, float* obs_dev, float* kernel_ms_total) {
-  if (!e || !policy || !actions_dev || !kernel_ms_total) return set_err(PP3_ERR_ARG, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  const int rc = pp3_rollout_policy(e, policy, nsteps, actions_dev, reward_dev, done_dev, obs_dev, e->stream);
-  if (rc) return rc;
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipEventSynchronize(e->ev1));
-  HIPCHK(hipEventElapsedTime(kernel_ms_total, e->ev0, e->ev1));
-  return PP3_OK;
-}
-
-int pp3_rollout_policy_sample_timed(pp3_env_t* e, pp3_policy_t* policy, int32_t nsteps, const uint32_t* key,
-                                    uint32_t* key_out, float* actions_dev, float* raw_dev, float* logp_dev,
-                                    float* reward_dev, float* done_dev, float* obs_dev, float* kernel_ms_total) {
-  if (!e || !policy || !key || !key_out || !actions_dev || !kernel_ms_total) return set_err(PP3_ERR_ARG, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  const int rc = pp3_rollout_policy_sample(e, policy, nsteps, key, key_out, actions_dev, raw_dev, logp_dev, reward_dev,
-                                           done_dev, obs_dev, e->stream);
-  if (rc) return rc;
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipEventSynchronize(e->ev1));
-  HIPCHK(hipEventElapsedTime(kernel_ms_total, e->ev0, e->ev1));
-  return PP3_OK;
-}
-
 }  // extern "C"
+
+// The template kernels of this library, the ones the launches above take (with fill_uniform_kernel,
+// trunc_row_kernel and outputs_to_host_kernel: 27 kernels).  Instantiated here, in this order, so
+// that the order of the functions in the code object does not follow the order in which host code
+// happens to name them: an edit to the launch layer leaves the device code byte for byte.
+#define PP3_STEP(NC, FUSED, NWV, CULL, SAMPLE, CAPS, ARGS) \
+  template __global__ void pp3::env_step_kernel<NC, FUSED, NWV, CULL, SAMPLE, pp3::CAPS>(pp3::ARGS)
+#define PP3_STEPS_NWV1(FUSED, CULL)                                \
+  PP3_STEP(8, FUSED, 1, CULL, false, CapsSmall, StepArgs);         \
+  PP3_STEP(8, FUSED, 1, CULL, false, CapsMax, StepArgs);           \
+  PP3_STEP(16, FUSED, 1, CULL, false, CapsMax, StepArgs)
+#define PP3_STEPS_POLICY(SAMPLE, ARGS)                             \
+  PP3_STEP(8, true, pp3pol::NWAVE, true, SAMPLE, CapsSmall, ARGS); \
+  PP3_STEP(8, true, pp3pol::NWAVE, true, SAMPLE, CapsMax, ARGS);   \
+  PP3_STEP(8, true, pp3pol::NWAVE, false, SAMPLE, CapsSmall, ARGS); \
+  PP3_STEP(8, true, pp3pol::NWAVE, false, SAMPLE, CapsMax, ARGS)
+template __global__ void pp3::env_reset_kernel<8>(pp3::ResetArgs);
+template __global__ void pp3::env_reset_kernel<16>(pp3::ResetArgs);
+PP3_STEPS_NWV1(true, true);
+PP3_STEPS_NWV1(false, true);
+PP3_STEPS_NWV1(true, false);
+PP3_STEPS_NWV1(false, false);
+#ifndef PP3_PHASE_PROF  // (the diagnostic builds have no fused policy kernel)
+PP3_STEPS_POLICY(false, PolicyStepArgs);
+PP3_STEPS_POLICY(true, SamplePolicyStepArgs);
+#endif
+template __global__ void pp3::physics_kernel<8>(pp3::PhysArgs);
+template __global__ void pp3::physics_kernel<16>(pp3::PhysArgs);
+#undef PP3_STEPS_POLICY
+#undef PP3_STEPS_NWV1
+#undef PP3_STEP

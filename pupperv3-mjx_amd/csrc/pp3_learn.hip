@@ -40,6 +40,7 @@
 #include <string>
 #include <vector>
 
+#include "pp3_env_host.h"
 #include "pp3_mlp.h"
 #include "pupper_hip.h"
 
@@ -1072,39 +1073,13 @@ int pp3_learner_normalizer_update(pp3_learner_t* L, const float* obs, int64_t ro
 }  // extern "C"
 
 // ---- the device draws ----
-// Host restatement of threefry and of `key, sub = split(key)` (pp3_env.hip's host_threefry is the
-// model), for the shuffle's per-round keys.
-static void learn_host_threefry(uint32_t k0, uint32_t k1, uint32_t x0, uint32_t x1, uint32_t& y0, uint32_t& y1) {
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  static const int rot[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-  x0 += k0;
-  x1 += k1;
-  for (int i = 0; i < 5; i++) {
-    for (int q = 0; q < 4; q++) {
-      x0 += x1;
-      x1 = (x1 << rot[i & 1][q]) | (x1 >> (32 - rot[i & 1][q]));
-      x1 ^= x0;
-    }
-    x0 += ks[(i + 1) % 3];
-    x1 += ks[(i + 2) % 3] + (uint32_t)(i + 1);
-  }
-  y0 = x0;
-  y1 = x1;
-}
-// key, sub = jax.random.split(key)
+// key, sub = jax.random.split(key) on the host (pp3_env_host.h host_split), for the shuffle's
+// per-round keys
 static void learn_host_split(HeadKey& key, HeadKey& sub, int part) {
-  uint32_t a0, a1, b0, b1;
-  if (part) {
-    learn_host_threefry(key.a, key.b, 0u, 0u, a0, a1);
-    learn_host_threefry(key.a, key.b, 0u, 1u, b0, b1);
-    key = HeadKey{a0, a1};
-    sub = HeadKey{b0, b1};
-  } else {  // flat words [y0(0,2), y0(1,3), y1(0,2), y1(1,3)]: key i = words 2i, 2i + 1
-    learn_host_threefry(key.a, key.b, 0u, 2u, a0, a1);
-    learn_host_threefry(key.a, key.b, 1u, 3u, b0, b1);
-    key = HeadKey{a0, b0};
-    sub = HeadKey{a1, b1};
-  }
+  uint32_t w[4];
+  host_split(key.a, key.b, part, w);
+  key = HeadKey{w[0], w[1]};
+  sub = HeadKey{w[2], w[3]};
 }
 
 static int sort_slots(int n) {

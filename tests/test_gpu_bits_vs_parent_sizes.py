@@ -25,6 +25,10 @@ rows, fused and as single-step launches):
   policy rollout and sampled policy rollout, 16 envs x 3 steps        (NWV = 8, observation tile)
   physics_kernel on 8 envs over the boxes, knees-down envs (more than 32 constraint rows) sharing
   their waves with standing envs, and the same envs re-paired so that no wave mixes, 1 and 3 substeps
+
+Without fixtures (3 envs x 2 steps, the fused launch against the per-step path): the instantiations
+that the cases above leave out -- the cull with the generic caps at contact cap 8 and 16, fused and
+single-step, and the policy rollouts with the generic caps (flat; with the cull; sampled with the cull).
 """
 import os
 
@@ -108,7 +112,8 @@ def _both_kernels(path, case, variant, n=6, K=4, seed=40, setup=None, episode=Fa
                 got[mode + "_episode"] = _bits(e._get(_abi.F_EPISODE))
         finally:
             e.close()
-    _check_or_record(case, got)
+    if case is not None:  # (None: no fixture, the two launch kinds against each other only)
+        _check_or_record(case, got)
     for k in ("state", "obs", "reward", "done", "buf_obs", "buf_reward", "buf_done", "metrics"):
         np.testing.assert_array_equal(got["fused_" + k], got["single_" + k], err_msg=k)
     return got
@@ -195,6 +200,61 @@ def test_policy_rollouts(flat_path, sample):
         dp.close()
         e.close()
     _check_or_record("policy_sample_16x3" if sample else "policy_16x3", got)
+
+
+@pytest.mark.parametrize("over", [dict(observation_history=3), dict(max_contacts=16)], ids=["h3", "nc16"])
+def test_cull_generic_fused_equals_single(box_path, over):
+    """The CULL instantiations with the generic caps, contact cap 8 and 16, which no case above
+    launches: 3 envs (the padded half wave runs) x 2 steps over the rails, one fused launch against
+    single-step launches."""
+    def setup(e, st):
+        assert e._L.pp3_narrow_cull(e._h) == 1
+        _over_rails(e, st, seed=48)
+
+    _both_kernels(box_path, None, GENERIC, n=3, K=2, seed=49, setup=setup, **over)
+
+
+@pytest.mark.parametrize("boxes,sample", [(False, False), (True, False), (True, True)])
+def test_policy_rollouts_generic_equal_per_step(flat_path, box_path, boxes, sample):
+    """The fused policy rollouts with the generic caps (observation_history 3: the MLP reads the
+    observations from global memory), flat and with the cull, deterministic and sampled: 3 envs x 2
+    steps, bit-equal to the per-step path (the stand-alone policy kernel, then a step)."""
+    from pupperv3_mjx import export, rng
+    from test_gpu_policy import _policy
+    from test_gpu_policy_sample import _assert_same, _loop_reference, _training
+    n, K = 3, 2
+    envs = [PupperV3Env(**common.fixture_kwargs(box_path if boxes else flat_path, observation_history=3), num_envs=n)
+            for _ in range(2)]
+    dp = export.DevicePolicy(_training([108, 64, 24]) if sample else _policy([108, 64, 24], "elu"))
+    ab = _lib.DeviceBuffer(n * 12 * 4)
+    try:
+        for e in envs:
+            assert e._L.pp3_rollout_policy_fused(e._h) == 1 and e._L.pp3_narrow_cull(e._h) == int(boxes)
+            _assert_variant(e, GENERIC, policy=True)
+        s1, s2 = envs[0].reset(make_keys(50, n)), envs[1].reset(make_keys(50, n))
+        if sample:
+            key = rng.PRNGKey(51)
+            s1, tr, k1 = envs[0].rollout_policy_sample(s1, dp, K, key)
+            s2, ref, k2 = _loop_reference(envs[1], envs[1], s2, dp, K, key)
+            _assert_same(tr, ref)
+            np.testing.assert_array_equal(k1, k2)
+        else:
+            s1, tr = envs[0].rollout_policy(s1, dp, K)
+            for t in range(K):
+                dp.act_env(envs[1], ab.ptr.value)
+                envs[1].synchronize()
+                a = np.zeros((n, 12), dtype=np.float32)
+                ab.download(a)
+                s2 = envs[1].step(s2, a)
+                np.testing.assert_array_equal(tr["action"][t], a)
+                for k in ("obs", "reward", "done"):
+                    np.testing.assert_array_equal(tr[k][t], getattr(s2, k), err_msg=k)
+        np.testing.assert_array_equal(s1._record, s2._record)
+    finally:
+        ab.free()
+        dp.close()
+        for e in envs:
+            e.close()
 
 
 def _physics(e, states, tag):
