@@ -587,6 +587,56 @@ int pp3_gae(int32_t device, int32_t nsteps, int32_t n, int64_t row_stride, const
             float discount, float lambda, float reward_scaling, float* vs, float* adv, void* stream);
 const char* pp3_ppo_last_error(void);
 
+/* ---- PPO evaluation: episode metrics and their mean / std (additive; PP3_ABI_VERSION stays 2) ----
+ * What Brax's Evaluator reports ([ext] brax 0.12.1 envs/wrappers/training.py EvalWrapper and
+ * training/acting.py Evaluator, restated from memory; what is written here is the contract).  Free
+ * functions on raw device pointers, in pp3_gae's style; errors through pp3_ppo_last_error().
+ *
+ * The accumulator acc is f32[PP3_EVAL_WORDS][n], column c of env i at acc[c * n + i]:
+ *   columns 0 .. 19   episode_metrics: total_dist, the 18 reward terms in PP3_REWARD_* order (the 19
+ *                     words of PP3_F_METRICS), then reward
+ *   PP3_EVAL_ACTIVE   active_episodes: 1 until the env's first done, 0 afterwards
+ *   PP3_EVAL_STEPS    episode_steps: the episode counter at the env's first done
+ * pp3_eval_reset: all zeros, active = 1.
+ * pp3_eval_accumulate: one wrapper step (auto-reset mode) of every env, from the env's buffers after
+ * that step: reward [n] and done [n] (PP3_F_REWARD, PP3_F_DONE), metrics [n][metrics_stride]
+ * (PP3_F_METRICS, the first PP3_NMETRIC words of a row) and episode [n][episode_stride]
+ * (PP3_F_EPISODE, word PP3_EP_STEPS of a row, which after a done step still holds the finished
+ * episode's count).  Per env, f32, * and + each rounded on their own (no fused multiply-add):
+ *   episode_steps      = active != 0 ? steps : episode_steps
+ *   episode_metrics[c] = episode_metrics[c] + x[c] * active       x = (metrics[0 .. 18], reward)
+ *   active             = active * (1 - done)
+ * pp3_eval_accumulate_rows: the same three lines on the reward column, active and episode_steps for
+ * the nsteps wrapper steps of a fused launch, from its reward / done trajectories [nsteps][n] (row
+ * stride row_stride floats), t = 0 .. nsteps-1 in step order, with steps = (step0 + t + 1) *
+ * action_repeat: the episode counter of an env that was reset step0 wrapper steps before row 0 and
+ * has not been done since, which is every env that is still active.  Columns 0 .. 18 are not touched.
+ * pp3_eval_reduce: out42[k] = mean and out42[PP3_EVAL_NOUT + k] = population standard deviation
+ * (ddof 0) over the n envs of reduced column k: k < 20 the metrics columns, k = 20 episode_steps.
+ * One 1024-lane workgroup, f32, every operation rounded on its own, in this order: lane i adds
+ * envs i, i + 1024, .. ascending from 0; the 1024 lane sums meet in a binary tree (for s = 512,
+ * 256, .. 1: sum[j] = sum[j] + sum[j + s], j < s); mean = sum / n; the second pass sums (x - mean) *
+ * (x - mean) in the same order; std = sqrt(that sum / n).  Both quotients and the root are correctly
+ * rounded (one residual step on the build's fast division and square root; rare double roundings
+ * excepted).  No atomics: a call repeats bit for bit.
+ * One kernel each on `stream` (NULL = default stream) of `device`, one lane per env for the first
+ * three.  PP3_ERR_ARG (nothing launched): a null pointer, n < 1, nsteps < 1, metrics_stride <
+ * PP3_NMETRIC, episode_stride < PP3_EP_STRIDE, row_stride < n, step0 < 0, action_repeat < 1, (step0 +
+ * nsteps) * action_repeat >= 2^24 (the counter stays exact in f32), or the accumulator (pp3_eval_reduce:
+ * out42) overlapping an input. */
+#define PP3_EVAL_NCOL 20
+#define PP3_EVAL_ACTIVE 20
+#define PP3_EVAL_STEPS 21
+#define PP3_EVAL_WORDS 22
+#define PP3_EVAL_NOUT 21
+int pp3_eval_reset(int32_t device, int32_t n, float* acc, void* stream);
+int pp3_eval_accumulate(int32_t device, int32_t n, const float* reward, const float* done, const float* metrics,
+                        int64_t metrics_stride, const float* episode, int64_t episode_stride, float* acc,
+                        void* stream);
+int pp3_eval_accumulate_rows(int32_t device, int32_t nsteps, int32_t n, int64_t row_stride, const float* reward,
+                             const float* done, int32_t step0, int32_t action_repeat, float* acc, void* stream);
+int pp3_eval_reduce(int32_t device, int32_t n, const float* acc, float* out42, void* stream);
+
 /* ---- PPO learner: loss gradients, Adam, weight reload (additive; PP3_ABI_VERSION stays 2) ----
  * One PPO iteration on the env's stream with no host round trip: collect, per minibatch loss +
  * gradient + Adam, reload the actor and the critic, collect again (csrc/pp3_learn.hip).  All f32.

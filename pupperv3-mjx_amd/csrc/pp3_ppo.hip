@@ -10,6 +10,14 @@
 // contracts them into fused multiply-adds by default, and HIP's __fmul_rn / __fadd_rn are plain
 // operators in its headers, contracted like any other: a first version built on them was 1 ulp
 // off the restatement).
+//
+// PPO evaluation (pp3_eval_*): Brax's EvalWrapper accumulator and the Evaluator's mean / std over the
+// eval envs, in the same style.  The accumulator is column-major ([22][n]), so one lane per env reads
+// and writes every column coalesced; pp3_eval_accumulate follows one wrapper step and reads the env's
+// own reward / done / metrics / episode buffers, pp3_eval_accumulate_rows follows a fused K-step
+// launch and chains over its reward / done rows with the loads a group ahead, as gae_kernel does.
+// pp3_eval_reduce is one 1024-lane workgroup with the learner's scalar-sum order (csrc/pp3_learn.hip
+// block_sum) and its residual-corrected quotient and square root, restated here under contract(off).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -92,6 +100,156 @@ __global__ __launch_bounds__(GAE_BLOCK) void gae_kernel(GaeArgs a) {
   }
 }
 
+// ---- PPO evaluation ----
+constexpr int EVAL_NCOL = PP3_EVAL_NCOL;   // episode_metrics: total_dist, the 18 reward terms, reward
+constexpr int EVAL_ACTIVE = PP3_EVAL_ACTIVE;
+constexpr int EVAL_STEPS = PP3_EVAL_STEPS;
+constexpr int EVAL_WORDS = PP3_EVAL_WORDS;
+constexpr int EVAL_NOUT = PP3_EVAL_NOUT;   // reduced columns: the 20 metrics, then episode_steps
+constexpr int EVAL_BLOCK = 256;
+constexpr int EVAL_U = 4;                  // steps whose loads are in flight together
+constexpr int EVAL_RED = 1024;             // the reduce's single workgroup
+
+__global__ __launch_bounds__(EVAL_BLOCK) void eval_reset_kernel(int n, float* __restrict__ acc) {
+  const size_t idx = (size_t)blockIdx.x * EVAL_BLOCK + threadIdx.x;
+  const size_t n0 = (size_t)n;
+  if (idx >= n0 * EVAL_WORDS) return;
+  acc[idx] = (idx >= n0 * EVAL_ACTIVE && idx < n0 * (EVAL_ACTIVE + 1)) ? 1.0f : 0.0f;
+}
+
+struct EvalStepArgs {
+  const float *reward, *done;  // [n]
+  const float* metrics;        // [n][metrics_stride], PP3_NMETRIC words read
+  const float* episode;        // [n][episode_stride], word PP3_EP_STEPS read
+  float* acc;                  // [EVAL_WORDS][n]
+  int64_t metrics_stride, episode_stride;
+  int n;
+};
+
+// One wrapper step.  A lane's 19 metric words are consecutive, so the wave's 19 loads walk the same
+// cache lines: each line is fetched once; the accumulator columns are coalesced.
+__global__ __launch_bounds__(EVAL_BLOCK) void eval_accumulate_kernel(EvalStepArgs a) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * EVAL_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const size_t n = (size_t)a.n;
+  const float active = a.acc[n * EVAL_ACTIVE + i];
+  const float* m = a.metrics + (size_t)i * (size_t)a.metrics_stride;
+  float x[EVAL_NCOL];
+#pragma unroll
+  for (int c = 0; c < PP3_NMETRIC; c++) x[c] = m[c];
+  x[EVAL_NCOL - 1] = a.reward[i];
+  const float d = a.done[i];
+  const float steps = a.episode[(size_t)i * (size_t)a.episode_stride + PP3_EP_STEPS];
+  if (active != 0.0f) a.acc[n * EVAL_STEPS + i] = steps;
+#pragma unroll
+  for (int c = 0; c < EVAL_NCOL; c++) {
+    const float em = a.acc[n * c + i];
+    a.acc[n * c + i] = em + x[c] * active;
+  }
+  a.acc[n * EVAL_ACTIVE + i] = active * (1.0f - d);
+}
+
+struct EvalRowsArgs {
+  const float *reward, *done;  // [nsteps][row_stride]
+  float* acc;
+  int64_t row_stride;
+  int nsteps, n, step0, action_repeat;
+};
+
+struct EvalRows {
+  float r[EVAL_U], d[EVAL_U];
+};
+
+// rows t0 .. t0 + EVAL_U - 1 of lane i; a row past the end reads the last row again (in bounds, and
+// the chain does not use it), which keeps the loads free of branches
+__device__ __forceinline__ void eval_load(const EvalRowsArgs& a, int t0, int i, EvalRows& w) {
+#pragma unroll
+  for (int j = 0; j < EVAL_U; j++) {
+    const int t = min(t0 + j, a.nsteps - 1);
+    const size_t at = (size_t)t * (size_t)a.row_stride + (size_t)i;
+    w.r[j] = a.reward[at];
+    w.d[j] = a.done[at];
+  }
+}
+
+// The K steps of a fused launch on the reward column, active and episode_steps: a serial chain per
+// lane in step order, the next group's loads issued ahead of this group's chain.
+__global__ __launch_bounds__(EVAL_BLOCK) void eval_rows_kernel(EvalRowsArgs a) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * EVAL_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const size_t n = (size_t)a.n;
+  float em = a.acc[n * (EVAL_NCOL - 1) + i];
+  float active = a.acc[n * EVAL_ACTIVE + i];
+  float es = a.acc[n * EVAL_STEPS + i];
+  EvalRows cur, nxt;
+  eval_load(a, 0, i, cur);
+  for (int t0 = 0; t0 < a.nsteps; t0 += EVAL_U) {
+    eval_load(a, t0 + EVAL_U, i, nxt);
+#pragma unroll
+    for (int j = 0; j < EVAL_U; j++) {
+      const int t = t0 + j;
+      if (t < a.nsteps) {
+        if (active != 0.0f) es = (float)((a.step0 + t + 1) * a.action_repeat);  // (exact: below 2^24)
+        em = em + cur.r[j] * active;
+        active = active * (1.0f - cur.d[j]);
+      }
+    }
+    cur = nxt;
+  }
+  a.acc[n * (EVAL_NCOL - 1) + i] = em;
+  a.acc[n * EVAL_ACTIVE + i] = active;
+  a.acc[n * EVAL_STEPS + i] = es;
+}
+
+// pp3_learn.hip's div_rn and block_sum (a / b with one residual step on the build's fast division;
+// lane partial sums met in a binary tree in LDS), restated for this file's kernels
+__device__ __forceinline__ float eval_div_rn(float a, float b) {
+  const float q = a / b;
+  return fmaf(fmaf(-q, b, a), 1.0f / b, q);
+}
+
+__device__ __forceinline__ float eval_block_sum(float v, float* sh) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  __syncthreads();
+  sh[tid] = v;
+  __syncthreads();
+  for (int s = EVAL_RED / 2; s > 0; s >>= 1) {
+    if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// out[k] = mean, out[EVAL_NOUT + k] = population std over the n envs of reduced column k, one
+// workgroup: lane i adds envs i, i + 1024, .. ascending, then the tree; two passes per column.
+__global__ __launch_bounds__(EVAL_RED) void eval_reduce_kernel(int n, const float* __restrict__ acc,
+                                                               float* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ float sh[EVAL_RED];
+  const float fn = (float)n;
+  for (int k = 0; k < EVAL_NOUT; k++) {
+    const float* col = acc + (size_t)n * (k < EVAL_NCOL ? k : EVAL_STEPS);
+    float s = 0.0f;
+    for (int e = threadIdx.x; e < n; e += EVAL_RED) s = s + col[e];
+    const float mean = eval_div_rn(eval_block_sum(s, sh), fn);
+    float q = 0.0f;
+    for (int e = threadIdx.x; e < n; e += EVAL_RED) {
+      const float d = col[e] - mean;
+      q = q + d * d;
+    }
+    const float var = eval_div_rn(eval_block_sum(q, sh), fn);
+    if (threadIdx.x == 0) {
+      float sd = sqrtf(var);  // (the build's fast sqrt is within 1 ulp; one residual step)
+      if (sd > 0.0f && sd < INFINITY) sd = fmaf(fmaf(-sd, sd, var), 0.5f / sd, sd);
+      out[k] = mean;
+      out[EVAL_NOUT + k] = sd;
+    }
+  }
+}
+
 }  // namespace pp3ppo
 
 using namespace pp3ppo;
@@ -140,6 +298,90 @@ int pp3_gae(int32_t device, int32_t nsteps, int32_t n, int64_t row_stride, const
   a.lambda = lambda;
   a.reward_scaling = reward_scaling;
   hipLaunchKernelGGL(gae_kernel, dim3((n + GAE_BLOCK - 1) / GAE_BLOCK), dim3(GAE_BLOCK), 0, (hipStream_t)stream, a);
+  PPOHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+// [p, p + np) and [q, q + nq) (floats) share a word
+static bool eval_overlap(const float* p, size_t np, const float* q, size_t nq) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + 4 * nq && b < a + 4 * np;
+}
+
+int pp3_eval_reset(int32_t device, int32_t n, float* acc, void* stream) {
+  if (!acc) return ppo_err(PP3_ERR_ARG, "pp3_eval_reset: null argument");
+  if (n < 1) return ppo_err(PP3_ERR_ARG, "pp3_eval_reset: n must be >= 1");
+  PPOHIP(hipSetDevice(device));
+  const size_t words = (size_t)n * EVAL_WORDS;
+  hipLaunchKernelGGL(eval_reset_kernel, dim3((unsigned)((words + EVAL_BLOCK - 1) / EVAL_BLOCK)), dim3(EVAL_BLOCK), 0,
+                     (hipStream_t)stream, n, acc);
+  PPOHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_eval_accumulate(int32_t device, int32_t n, const float* reward, const float* done, const float* metrics,
+                        int64_t metrics_stride, const float* episode, int64_t episode_stride, float* acc,
+                        void* stream) {
+  if (!reward || !done || !metrics || !episode || !acc)
+    return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate: null argument");
+  if (n < 1) return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate: n must be >= 1");
+  if (metrics_stride < PP3_NMETRIC) return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate: metrics_stride shorter than PP3_NMETRIC");
+  if (episode_stride < PP3_EP_STRIDE) return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate: episode_stride shorter than PP3_EP_STRIDE");
+  const size_t n0 = (size_t)n, words = n0 * EVAL_WORDS;
+  if (eval_overlap(acc, words, reward, n0) || eval_overlap(acc, words, done, n0) ||
+      eval_overlap(acc, words, metrics, n0 * (size_t)metrics_stride) ||
+      eval_overlap(acc, words, episode, n0 * (size_t)episode_stride))
+    return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate: the accumulator aliases an input");
+  PPOHIP(hipSetDevice(device));
+  EvalStepArgs a;
+  a.reward = reward;
+  a.done = done;
+  a.metrics = metrics;
+  a.episode = episode;
+  a.acc = acc;
+  a.metrics_stride = metrics_stride;
+  a.episode_stride = episode_stride;
+  a.n = n;
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3((n + EVAL_BLOCK - 1) / EVAL_BLOCK), dim3(EVAL_BLOCK), 0,
+                     (hipStream_t)stream, a);
+  PPOHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_eval_accumulate_rows(int32_t device, int32_t nsteps, int32_t n, int64_t row_stride, const float* reward,
+                             const float* done, int32_t step0, int32_t action_repeat, float* acc, void* stream) {
+  if (!reward || !done || !acc) return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate_rows: null argument");
+  if (nsteps < 1 || n < 1) return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate_rows: nsteps and n must be >= 1");
+  if (row_stride < n) return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate_rows: row_stride shorter than n");
+  if (step0 < 0 || action_repeat < 1 || ((int64_t)step0 + nsteps) * action_repeat >= (1 << 24))
+    return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate_rows: step0 >= 0, action_repeat >= 1 and (step0 + nsteps) * "
+                                "action_repeat < 2^24 are required");
+  const size_t words = (size_t)n * EVAL_WORDS, rows = (size_t)(nsteps - 1) * (size_t)row_stride + (size_t)n;
+  if (eval_overlap(acc, words, reward, rows) || eval_overlap(acc, words, done, rows))
+    return ppo_err(PP3_ERR_ARG, "pp3_eval_accumulate_rows: the accumulator aliases an input");
+  PPOHIP(hipSetDevice(device));
+  EvalRowsArgs a;
+  a.reward = reward;
+  a.done = done;
+  a.acc = acc;
+  a.row_stride = row_stride;
+  a.nsteps = nsteps;
+  a.n = n;
+  a.step0 = step0;
+  a.action_repeat = action_repeat;
+  hipLaunchKernelGGL(eval_rows_kernel, dim3((n + EVAL_BLOCK - 1) / EVAL_BLOCK), dim3(EVAL_BLOCK), 0,
+                     (hipStream_t)stream, a);
+  PPOHIP(hipGetLastError());
+  return PP3_OK;
+}
+
+int pp3_eval_reduce(int32_t device, int32_t n, const float* acc, float* out42, void* stream) {
+  if (!acc || !out42) return ppo_err(PP3_ERR_ARG, "pp3_eval_reduce: null argument");
+  if (n < 1) return ppo_err(PP3_ERR_ARG, "pp3_eval_reduce: n must be >= 1");
+  if (eval_overlap(acc, (size_t)n * EVAL_WORDS, out42, 2 * EVAL_NOUT))
+    return ppo_err(PP3_ERR_ARG, "pp3_eval_reduce: the output aliases the accumulator");
+  PPOHIP(hipSetDevice(device));
+  hipLaunchKernelGGL(eval_reduce_kernel, dim3(1), dim3(EVAL_RED), 0, (hipStream_t)stream, n, acc, out42);
   PPOHIP(hipGetLastError());
   return PP3_OK;
 }

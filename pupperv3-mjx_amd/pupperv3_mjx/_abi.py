@@ -37,6 +37,8 @@ COMM_ID_BYTES = 128  # PP3_COMM_ID_BYTES (ncclUniqueId)
 REDUCE_SUM, REDUCE_MAX = 0, 1
 LEARN_MAX_WORLD = 64  # PP3_LEARN_MAX_WORLD: ranks of the learner's rank-ordered reduces
 SHUFFLE_MAX_ENVS = 65536  # pp3_permute_by_bits / pp3_learner_shuffle_env_index: the one-workgroup sort's range
+# the PPO evaluator's accumulator f32[EVAL_WORDS][n] (PP3_EVAL_*): 20 episode_metrics columns, active, episode_steps
+EVAL_NCOL, EVAL_ACTIVE, EVAL_STEPS, EVAL_WORDS, EVAL_NOUT = 20, 20, 21, 22, 21
 
 DR_FRICTION, DR_KP, DR_KD, DR_BASE_IPOS, DR_INERTIA, DR_MASS = 0, 1, 2, 3, 6, 48
 

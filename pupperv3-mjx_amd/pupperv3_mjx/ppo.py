@@ -36,12 +36,22 @@ The index is bit-identical to the host path's.  The noise agrees with it to erfi
 uniform is jax's bit for bit on both paths, then the host path rounds scipy's float64 erfinv to f32
 where the device evaluates the device library's erfinvf, and neither is bit-pinned to XLA's erf_inv.
 
-Not here (follow-ups): learning-rate schedules (`lr` is a per-call argument), bf16 / mixed precision.
+The loop around it is `train` (Brax's ppo.train schedule: `eval_schedule`): it resets the training
+envs, runs the iterations and evaluates with an `evaluator.Evaluator` before training and after every
+epoch, calling `progress_fn` and `policy_params_fn` at each evaluation; `learning_rate` may be a
+callable of the iteration index.
+
+    actor, critic, metrics = ppo.train(learner, wrap(env, 1000), wrap(eval_env, 1000), num_timesteps=10_000_000,
+                                       episode_length=1000, num_evals=10, key=key, progress_fn=progress)
+
+Not here (follow-ups): bf16 / mixed precision, a cross-rank reduce of the evaluation metrics.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Dict, List, Optional, Tuple
+import math
+import time
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -368,6 +378,28 @@ class PPOLearner:
         self.sync(actor, critic)
         return actor, critic
 
+    def deterministic_policy(self) -> DevicePolicy:
+        """A deployment handle of the current parameters (12 outputs: tanh of the head's mean, the
+        normaliser folded into layer 0 on the host in f32), for a deterministic evaluation.  It is a
+        snapshot built from downloads (waits for the stream); the caller closes it."""
+        layers = self.params()["policy"]
+        if self._norm is not None:
+            ns = self.normalizer_state()
+            inv = np.float32(1.0) / ns["std"].astype(np.float32)
+            k0, b0 = layers[0]
+            layers[0] = ((k0 * inv[:, None]).astype(np.float32),
+                         (b0 - (ns["mean"].astype(np.float32) * inv) @ k0).astype(np.float32))
+        kl, bl = layers[-1]
+        layers[-1] = (np.ascontiguousarray(kl[:, :_abi.NU]), np.ascontiguousarray(bl[:_abi.NU]))
+        src = self._dicts[0]
+        out = {k: v for k, v in src.items() if k not in ("layers", "distribution")}
+        out["layers"] = []
+        for i, (layer, (k, b)) in enumerate(zip(src["layers"], layers)):
+            last = i == len(layers) - 1
+            out["layers"].append(dict(layer, weights=[k, b], shape=[None, int(b.shape[0])],
+                                      activation="tanh" if last else layer["activation"]))
+        return DevicePolicy(out, self.device)
+
     def sync(self, device_policy: Optional[DevicePolicy], device_value: Optional[DevicePolicy], stream=None) -> None:
         """Reloads the handles (either may be None) from the current parameters, the normaliser
         folded into layer 0 (pp3_policy_load_params)."""
@@ -443,3 +475,102 @@ class PPOLearner:
             self.close()
         except Exception:
             pass
+
+
+def eval_schedule(num_timesteps: int, num_envs: int, unroll_length: int, action_repeat: int = 1,
+                  num_evals: int = 1) -> Dict[str, Any]:
+    """Brax ppo.train's schedule ([ext] brax 0.12.1 training/agents/ppo/train.py, from memory), with one
+    training_step per iteration: an iteration is num_envs * unroll_length * action_repeat env steps;
+    num_evals_after_init = max(num_evals - 1, 1) epochs of iterations_per_epoch = ceil(num_timesteps /
+    (num_evals_after_init * steps_per_iteration)) iterations each; one evaluation before training when
+    num_evals > 1 and one after every epoch.  eval_steps: the env-step count reported at each evaluation."""
+    if min(num_timesteps, num_envs, unroll_length, action_repeat, num_evals) < 1:
+        raise ValueError("num_timesteps, num_envs, unroll_length, action_repeat and num_evals must be >= 1")
+    spi = int(num_envs) * int(unroll_length) * int(action_repeat)
+    after = max(int(num_evals) - 1, 1)
+    ipe = int(math.ceil(int(num_timesteps) / (after * spi)))
+    first = int(num_evals) > 1
+    return dict(steps_per_iteration=spi, num_evals_after_init=after, iterations_per_epoch=ipe,
+                eval_before_training=first, total_iterations=after * ipe,
+                eval_steps=([0] if first else []) + [(e + 1) * ipe * spi for e in range(after)])
+
+
+def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episode_length: int, action_repeat: int = 1,
+          unroll_length: int = 20, num_minibatches: int = 1, num_updates_per_batch: int = 1,
+          learning_rate: Union[float, Callable[[int], float]] = 3e-4, num_evals: int = 1,
+          deterministic_eval: bool = False, key, progress_fn: Optional[Callable[[int, Dict[str, Any]], None]] = None,
+          policy_params_fn: Optional[Callable[..., None]] = None, shuffle: bool = True,
+          max_grad_norm: Optional[float] = None, normalize_observations: bool = False, device_rng: bool = True,
+          comm=None, **hparams):
+    """Brax's ppo.train loop around `learner.train_iteration` (the schedule: eval_schedule).  `env`
+    and `eval_env` are `wrappers.wrap`ped envs of this `episode_length` / `action_repeat`; `eval_env`
+    may also be a constructed `evaluator.Evaluator` (e.g. one on the reward path), or None to train
+    without evaluations.  Returns (actor, critic, metrics of the last evaluation or iteration).
+
+    Keys: k_train, k_env, k_eval = split(key, 3); the training envs reset with split(k_env, N); the
+    evaluator owns k_eval; iteration i takes `k_train, k_it = split(k_train)` and runs
+    train_iteration(key=k_it, lr=learning_rate(i) if callable).  At each evaluation
+    progress_fn(num_steps, metrics) and policy_params_fn(num_steps, learner.params(), normaliser
+    state or None) are called; metrics = the evaluator's dict with the last iteration's losses as
+    training/<name>, training/sps and training/walltime.  deterministic_eval: the evaluation runs
+    `learner.deterministic_policy()`, rebuilt from the parameters at every evaluation; otherwise it
+    samples from the actor.  normalize_observations: train_iteration(update_normalizer=True), which
+    needs PPOLearner(running_statistics=True).  comm: every rank trains on its own shard with its own
+    key and evaluates its own eval env; the evaluation metrics are not reduced across ranks."""
+    from .evaluator import Evaluator
+    base = _base(env)
+    n, part = base.num_envs, base._partitionable
+    for e in (env,) + (() if eval_env is None or isinstance(eval_env, Evaluator) else (eval_env,)):
+        if (getattr(e, "episode_length", None), getattr(e, "action_repeat", None)) != (int(episode_length),
+                                                                                      int(action_repeat)):
+            raise ValueError("train needs wrappers.wrap'ped envs of the given episode_length and action_repeat")
+    sched = eval_schedule(num_timesteps, n, unroll_length, action_repeat, num_evals)
+    k_train, k_env, k_eval = rng.split(np.asarray(key, dtype=np.uint32).reshape(2), 3, part)
+    state = env.reset(rng.split(k_env, n, part))
+    actor, critic = learner.make_policies()
+    if eval_env is None:
+        evaluator = None
+    elif isinstance(eval_env, Evaluator):
+        evaluator = eval_env
+    else:
+        evaluator = Evaluator(eval_env, actor, episode_length, action_repeat, key=k_eval,
+                              deterministic=deterministic_eval)
+    metrics: Dict[str, Any] = {}
+    walltime = 0.0
+
+    def evaluate(num_steps: int, training_metrics: Dict[str, Any]) -> Dict[str, Any]:
+        pol = learner.deterministic_policy() if evaluator.deterministic else actor
+        try:
+            m = evaluator.run_evaluation(training_metrics, policy=pol)
+        finally:
+            if pol is not actor:
+                pol.close()
+        if progress_fn is not None:
+            progress_fn(num_steps, m)
+        if policy_params_fn is not None:
+            policy_params_fn(num_steps, learner.params(), learner.normalizer_state() if learner._norm is not None else None)
+        return m
+
+    if evaluator is not None and sched["eval_before_training"]:
+        metrics = evaluate(0, {})
+    it = 0
+    for epoch in range(sched["num_evals_after_init"]):
+        t0 = time.time()
+        for _ in range(sched["iterations_per_epoch"]):
+            k_train, k_it = rng.split(k_train, 2, part)
+            lr = learning_rate(it) if callable(learning_rate) else learning_rate
+            state, losses, _ = learner.train_iteration(
+                env, state, k_it, actor, critic, unroll_length, num_minibatches=num_minibatches,
+                num_updates_per_batch=num_updates_per_batch, lr=float(lr), shuffle=shuffle, max_grad_norm=max_grad_norm,
+                update_normalizer=normalize_observations, comm=comm, device_rng=device_rng, **hparams)
+            it += 1
+        dt = time.time() - t0  # (train_iteration's metrics download has waited for the epoch's work)
+        walltime += dt
+        metrics = {f"training/{k}": v for k, v in losses.items()}
+        metrics["training/sps"] = sched["iterations_per_epoch"] * sched["steps_per_iteration"] / dt
+        metrics["training/walltime"] = walltime
+        if evaluator is not None:
+            metrics = evaluate(it * sched["steps_per_iteration"], metrics)
+    if evaluator is not None and evaluator is not eval_env:
+        evaluator.close()
+    return actor, critic, metrics
