@@ -41,7 +41,7 @@ struct pp3_env {
   float* first_obs;
   int episode_length;
   int action_repeat;  // auto-reset mode: launches per wrapper step (1 otherwise)
-  float* terrain;  // TerrainRec rows (pp3_set_terrain), null until first set
+  float* terrain;  // TerrainRec[N padded to whole 16-env workgroups][nbox] (pp3_set_terrain), null until first set
   int nbox;        // world box-geom slots in the model
   int cull;        // DevModel::cull_on: steps launch env_step_kernel<..., CULL = true>
   int partitionable;  // the config's rng_partitionable (the sampled policy rollout's host key chain)

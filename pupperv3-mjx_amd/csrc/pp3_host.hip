@@ -14,8 +14,13 @@
 
 #include "pp3_device.h"
 #include "pp3_env_host.h"
+#include "pp3_mlp.h"
 
 using namespace pp3;
+
+// envs per workgroup of the largest launch (the policy rollouts: one MLP tile, two envs per wave)
+constexpr int TERRAIN_ROW_PAD = pp3pol::TILE;
+static_assert(TERRAIN_ROW_PAD == 2 * pp3pol::NWAVE && TERRAIN_ROW_PAD % 2 == 0, "terrain rows cover whole workgroups");
 
 static thread_local std::string g_err;
 int set_err(int code, const std::string& msg) {
@@ -204,18 +209,20 @@ int pp3_set_terrain(pp3_env_t* e, const float* boxes, int32_t n_boxes) {
       return set_err(PP3_ERR_ARG, "pp3_set_terrain: n_boxes must equal the model's world box-geom count (" +
                                       std::to_string(e->nbox) + ")");
     if (n_boxes == 0) return set_err(PP3_ERR_ARG, "pp3_set_terrain: the model has no box geoms to use as slots");
-    const size_t rows = (size_t)(e->N + 1) / 2 * 2;  // even: the kernel indexes by 2 * block + half
+    // The kernels index the table by the unclamped env slot of the launch: 2 * block + half in the
+    // one-wave launches, and every slot of the policy rollouts' whole TERRAIN_ROW_PAD-env workgroups
+    // (the waves past N still run the physics).  So the rows are padded to a multiple of the largest
+    // workgroup, and a padding row holds absent boxes.
+    const size_t rows = ((size_t)e->N + TERRAIN_ROW_PAD - 1) / TERRAIN_ROW_PAD * TERRAIN_ROW_PAD;
     std::vector<TerrainRec> rec(rows * n_boxes);
     memset(rec.data(), 0, rec.size() * sizeof(TerrainRec));
     for (size_t i = 0; i < rows; i++)
       for (int b = 0; b < n_boxes; b++) {
         TerrainRec& r = rec[i * n_boxes + b];
-        if (i >= (size_t)e->N) {  // padding row: absent boxes
-          r.p[2] = -1e4f;
-          continue;
-        }
-        const float* x = boxes + (i * n_boxes + b) * PP3_TERRAIN_BOX;
-        if (!(x[7] > 0 || x[8] > 0 || x[9] > 0)) {  // absent: far below the floor, zero size
+        const float* x = i < (size_t)e->N ? boxes + (i * n_boxes + b) * PP3_TERRAIN_BOX : nullptr;
+        // a padding row or an absent box: far below the floor, zero size, identity rotation (a zero
+        // rotation would map every sphere centre to the box centre: a contact with each)
+        if (!x || !(x[7] > 0 || x[8] > 0 || x[9] > 0)) {
           r.p[2] = -1e4f;
           r.R[0] = r.R[4] = r.R[8] = 1.0f;
           continue;

@@ -186,7 +186,10 @@ def env_with_model(path, model_struct, n, **kw):
     L = _lib.load()
     h = C.c_void_p()
     _lib.check(L.pp3_create(C.byref(model_struct), C.byref(e.config_struct), n, 0, C.byref(h)))
-    e._h, e._L = h, L
+    # as PupperV3Env.__init__ leaves them, so the whole host API (reset / step / rollout) works on it
+    from pupperv3_mjx.environment import _FlushingLib
+    e._h, e._raw, e._qb = h, L, None
+    e._L = _FlushingLib(e, L)
     _lib.check(L.pp3_set_pipeline_output(h, 1))
     e._keys_buf = _lib.DeviceBuffer(n * 8, 0)
     e._act_buf = _lib.DeviceBuffer(n * _abi.NU * 4, 0)

@@ -3,8 +3,6 @@ import ctypes as C
 import os
 import re
 
-import pytest
-
 from pupperv3_mjx import _abi, _lib
 
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
@@ -87,8 +85,9 @@ def test_loopback_transport_exports_the_rccl_api():
     import ctypes as C
     here = os.path.dirname(os.path.abspath(__file__))
     lb = os.path.join(here, "loopback", "libpp3_loopback_rccl.so")
-    if not os.path.exists(lb):
-        pytest.skip("loopback test build absent (make -C pupperv3-mjx_amd/csrc loopback)")
+    # build() always makes it: absent is an error, as in test_gpu_multirank.py (a skip here would let
+    # the multi-rank tests' transport go unchecked on a host without a GPU)
+    assert os.path.exists(lb), "loopback test build missing: make -C pupperv3-mjx_amd/csrc loopback (__graft_entry__.build)"
     T = C.CDLL(lb)
     for name in ("ncclGetUniqueId", "ncclCommInitRank", "ncclCommDestroy", "ncclAllGather", "ncclAllReduce",
                  "ncclSend", "ncclRecv", "ncclGroupStart", "ncclGroupEnd", "ncclGetErrorString"):
