@@ -862,6 +862,35 @@ int pp3_learner_shuffle_env_index(pp3_learner_t* learner, const uint32_t key[2],
                                   int32_t partitionable, void* stream);
 int pp3_learner_rng_buffers(pp3_learner_t* learner, int32_t** index_dev, int32_t* index_n, float** noise_dev,
                             int64_t* noise_count);
+
+/* ---- PPO learner: network initialisation on the device (additive; ABI stays 2) ----
+ * Restated from memory of jax `nn.initializers.lecun_uniform` (variance_scaling(1.0, "fan_in",
+ * "uniform")) and Brax `make_ppo_networks` (MLPs whose kernels take lecun_uniform and whose biases are
+ * zero); what is written here is the contract.
+ *
+ * pp3_learner_init_params overwrites both parameter blobs and zeroes both gradient blobs and both
+ * nets' Adam moments m and v, enqueued on `stream` with no host copy and no host synchronisation (one
+ * launch per net, one thread per blob element; the caller's Adam step count restarts at 0).  A call
+ * repeated with the same key gives the same bits, and so does every rank that passes the same key.
+ *
+ * Keys (two-way jax.random.split on the host, in the `partitionable` layout):
+ *   k_policy, k_value = split(key)
+ *   inside a net, for layer l = 0 .. L-1 in order:  k_net, k_l = split(k_net)
+ * This schedule is this library's own.  Flax derives a layer's key by folding the module's path into
+ * the init key, which depends on module names that cannot be pinned here; the distribution of every
+ * kernel is flax's, the stream behind it is not.
+ *
+ * Layer l with fan_in rows and `out` columns (blob layout [in][out] row-major, then the bias):
+ *   kernel element i = u_i * s
+ *   u_i = jax.random.uniform(k_l, (fan_in, out), float32, minval = -1, maxval = 1) flat element i, bit
+ *         for bit (count = fan_in * out; both counter layouts, the pre-0.5 one zero-padding an odd count)
+ *   s   = sqrtf(3.0f * (1.0f / (float)fan_in)), f32 on the host
+ *   one f32 multiply, no FMA contraction; every entry lies in [-s, s)
+ *   bias = 0
+ * pupperv3_mjx/ppo.py init_params is the same in numpy.
+ * PP3_ERR_ARG through pp3_learn_last_error() before any launch: a null learner or key; the blobs are
+ * untouched. */
+int pp3_learner_init_params(pp3_learner_t* learner, const uint32_t key[2], int32_t partitionable, void* stream);
 const char* pp3_learn_last_error(void);
 
 /* ---------------------------------------------------------------------------------------

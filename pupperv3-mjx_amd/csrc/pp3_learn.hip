@@ -27,6 +27,9 @@
 // (pp3_learner_shuffle_env_index: jax's _shuffle, per round a host split, a random-bits kernel and a
 // one-workgroup bitonic sort of (bits << 32) | i; the permute alone: pp3_permute_by_bits).
 //
+// The networks' first parameters (pp3_learner_init_params: lecun_uniform kernels from the same
+// uniform, zero biases, one thread per blob element, one launch per net over a layer table).
+//
 // Across ranks (data-parallel PPO over a pp3_comm_t): the gradient blobs and the metrics are packed
 // into one send, all-gathered, and added in rank order by one kernel (pp3_learner_allreduce_grads;
 // the kernel alone: pp3_learner_reduce_gathered); the normaliser's finish is cut in two around an
@@ -637,6 +640,39 @@ __global__ __launch_bounds__(NTHREAD) void shuffle_bits_kernel(HeadKey key, int 
   bits[i] = w;
 }
 
+// ---- network initialisation (pp3_learner_init_params): one launch per net over its whole blob ----
+// The layer table: blob elements [begin, begin + kcount) are layer l's kernel, element begin + j
+// being u_j * scale with u_j = jax.random.uniform(key, (kcount,), f32, -1, 1)[j]; the elements from
+// there to the next layer's begin (the blob's end for the last layer) are its bias, zero.
+struct InitLayer {
+  HeadKey key;
+  int begin, kcount;
+  float scale;
+};
+struct InitArgs {
+  InitLayer layer[PP3_POLICY_MAX_LAYERS];
+  int n_layers, count, part;
+  float *p, *g, *m, *v;  // parameters, gradients, Adam moments: [count] each
+};
+
+// one thread per blob element: the parameter, and zeros for its gradient and moments
+__global__ __launch_bounds__(NTHREAD) void init_params_kernel(InitArgs a) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * NTHREAD + threadIdx.x;
+  if (i >= a.count) return;
+  InitLayer ly = a.layer[0];  // the last layer that begins at or before i (begins ascend)
+#pragma unroll
+  for (int l = 1; l < PP3_POLICY_MAX_LAYERS; l++)
+    if (l < a.n_layers && i >= a.layer[l].begin) ly = a.layer[l];
+  const int j = i - ly.begin;
+  float w = 0.0f;
+  if (j < ly.kcount) w = pp3pol::head_uniform(ly.key, ly.kcount, j, -1.0f, a.part) * ly.scale;
+  a.p[i] = w;
+  a.g[i] = 0.0f;
+  a.m[i] = 0.0f;
+  a.v[i] = 0.0f;
+}
+
 // x := x[stable_argsort(bits)], one workgroup.  The keys are (bits[i] << 32) | i, all distinct, so
 // the order is the stable one whatever the network; slots n .. P-1 (P: n rounded up to a power of
 // two) hold all-ones keys, above every real key (i <= 65535), and end up last.  A bitonic network on
@@ -1173,6 +1209,34 @@ int pp3_learner_shuffle_env_index(pp3_learner_t* L, const uint32_t* key, int32_t
   }
   LHIP(hipGetLastError());
   L->idx_n = n;
+  return PP3_OK;
+}
+
+int pp3_learner_init_params(pp3_learner_t* L, const uint32_t* key, int32_t partitionable, void* stream) {
+  if (!L || !key) return lerr(PP3_ERR_ARG, "pp3_learner_init_params: null argument");
+  LHIP(hipSetDevice(L->device));
+  const int part = partitionable ? 1 : 0;
+  HeadKey k_net[2] = {HeadKey{key[0], key[1]}, HeadKey{0u, 0u}};
+  learn_host_split(k_net[0], k_net[1], part);  // k_policy, k_value = split(key)
+  for (int n = 0; n < 2; n++) {
+    const NetShape& s = L->net[n];
+    InitArgs a{};
+    a.n_layers = s.n_layers;
+    a.count = (int)s.count;  // (at most 8 layers of 577 x 576)
+    a.part = part;
+    a.p = L->blob[n][0]; a.g = L->blob[n][1]; a.m = L->blob[n][2]; a.v = L->blob[n][3];
+    for (int l = 0; l < s.n_layers; l++) {
+      HeadKey k_l{0u, 0u};
+      learn_host_split(k_net[n], k_l, part);  // k_net, k_l = split(k_net)
+      a.layer[l].key = k_l;
+      a.layer[l].begin = (int)s.off[l];
+      a.layer[l].kcount = s.K[l] * s.M[l];
+      a.layer[l].scale = sqrtf(3.0f * (1.0f / (float)s.K[l]));
+    }
+    hipLaunchKernelGGL(init_params_kernel, dim3((unsigned)((a.count + NTHREAD - 1) / NTHREAD)), dim3(NTHREAD), 0,
+                       (hipStream_t)stream, a);
+  }
+  LHIP(hipGetLastError());
   return PP3_OK;
 }
 

@@ -142,6 +142,9 @@ def load() -> C.CDLL:
         for name in ("pp3_learner_draw_noise", "pp3_permute_by_bits", "pp3_learner_shuffle_env_index",
                      "pp3_learner_rng_buffers"):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, "pp3_learner_init_params"):  # (network initialisation; absent from earlier builds run in kernel A/B)
+        L.pp3_learner_init_params.argtypes = [vp, vp, i32, vp]
+        L.pp3_learner_init_params.restype = C.c_int
     if hasattr(L, "pp3_eval_reduce"):  # (the PPO evaluator; absent from earlier builds run in kernel A/B)
         L.pp3_eval_reset.argtypes = [i32, i32, vp, vp]
         L.pp3_eval_accumulate.argtypes = [i32, i32, vp, vp, vp, i64, vp, i64, vp, vp]
@@ -224,6 +227,7 @@ EXPORTED_SYMBOLS = (
     "pp3_learner_allreduce_grads", "pp3_learner_reduce_gathered", "pp3_learner_normalizer_update_ranks",
     "pp3_comm_allgather_f32", "pp3_comm_device",
     "pp3_learner_draw_noise", "pp3_permute_by_bits", "pp3_learner_shuffle_env_index", "pp3_learner_rng_buffers",
+    "pp3_learner_init_params",
     "pp3_stream", "pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy",
     "pp3_set_terrain", "pp3_terrain_slots",
     "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_comm_rank", "pp3_comm_world",

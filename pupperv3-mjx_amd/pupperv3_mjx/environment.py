@@ -468,6 +468,7 @@ class PupperV3Env:
         self._act_i = 0
         self._lazy_extra = {}  # field id -> info hook (wrappers.AutoResetEpisodeEnv: the episode record)
         self._issue_capture = None  # () -> host data a wrapper attaches to each state when it is issued
+        self._dr_on = False  # per-env domain-randomisation rows are set (set_domain_randomization)
         self._field_elems = {f: self.device_field(f)[1] for f in (_abi.F_STATE, _abi.F_METRICS, _abi.F_PIPELINE)}
         self._field_elems[_abi.F_EPISODE] = _abi.EP_STRIDE
         off, self._snap_offsets = 0, {}
@@ -595,11 +596,13 @@ class PupperV3Env:
         """Upload the per-env parameters of a batched System (or None to disable DR)."""
         if sys_batched is None:
             _lib.check(self._L.pp3_set_dr(self._h, None))
+            self._dr_on = False
             return
         table = np.ascontiguousarray(sys_batched.dr_table(), dtype=np.float32)
         if table.shape[0] != self.num_envs:
             raise ValueError("DR batch size must equal num_envs")
         _lib.check(self._L.pp3_copy_field_from_host(self._h, _abi.F_DR, table.ctypes.data_as(C.c_void_p), table.nbytes))
+        self._dr_on = True
 
     # ------------------------------------------------------------------ terrain
     @property
@@ -651,6 +654,58 @@ class PupperV3Env:
         self._before_launch()
         a = np.ascontiguousarray(arr, dtype=np.float32)
         _lib.check(self._L.pp3_copy_field_from_host(self._h, field_id, a.ctypes.data_as(C.c_void_p), a.nbytes))
+
+    # ------------------------------------------------------------------ checkpoints
+    def _checkpoint_layout(self, episode_length: int = 0, action_repeat: int = 1) -> Dict[str, int]:
+        """What a state_dict's arrays depend on: a dict from an env where any of these differs is refused."""
+        c = self.config_struct
+        return dict(num_envs=self.num_envs, observation_history=self._observation_history,
+                    latency_len=int(c.latency_len), imu_latency_len=int(c.imu_latency_len), state_stride=self.stride,
+                    max_contacts=int(c.ncon_max) or 8, episode_length=int(episode_length),
+                    action_repeat=int(action_repeat), domain_randomization=int(self._dr_on),
+                    terrain_slots=self.terrain_slots, pipeline_output=int(self._pipeline_output))
+
+    def state_dict(self, extra_fields: Tuple[int, ...] = (), **layout) -> Dict[str, np.ndarray]:
+        """The env's device state as plain arrays (a checkpoint; ppo.save_checkpoint): the raw bits,
+        uint32 [num_envs][elements], of every per-env field a later step reads or a returned State
+        shows -- the state record (with each env's RNG words), obs, reward, done (the auto-reset reads
+        it at the start of the next step), metrics, and the pipeline record when pipeline_output is on
+        -- under "field_<id>", plus "layout_<name>" scalars naming what must match at load.  Issues the
+        queued steps and waits for the stream.  The domain-randomisation rows and the terrain are
+        configuration, not state: the caller sets them again as it did at first."""
+        fields = ((_abi.F_STATE, _abi.F_OBS, _abi.F_REWARD, _abi.F_DONE, _abi.F_METRICS)
+                  + ((_abi.F_PIPELINE,) if self._pipeline_output else ()) + tuple(extra_fields))
+        d = {f"layout_{k}": np.asarray(v, dtype=np.int64) for k, v in self._checkpoint_layout(**layout).items()}
+        d["fields"] = np.asarray(fields, dtype=np.int32)
+        for f in fields:
+            d[f"field_{f}"] = self._get(f).view(np.uint32)
+        return d
+
+    def load_state_dict(self, d: Dict[str, np.ndarray], extra_fields: Tuple[int, ...] = (), **layout) -> State:
+        """Puts a state_dict back on the device and returns the State it holds (`holds()` accepts it:
+        the next step uploads nothing).  ValueError, with nothing uploaded, when the dict is from an env
+        of another layout (num_envs, observation history, latency lengths, state stride, contact cap,
+        episode length, action repeat, domain randomisation on or off, terrain slots) or lacks a
+        field.  A live state of this env keeps its own data (it is snapshotted first, as before a
+        launch)."""
+        want = self._checkpoint_layout(**layout)
+        for k, v in want.items():
+            if f"layout_{k}" not in d or int(d[f"layout_{k}"]) != v:
+                got = int(d[f"layout_{k}"]) if f"layout_{k}" in d else None
+                raise ValueError(f"the state_dict is of another env: {k} is {got}, this env's is {v}")
+        fields = ((_abi.F_STATE, _abi.F_OBS, _abi.F_REWARD, _abi.F_DONE, _abi.F_METRICS)
+                  + ((_abi.F_PIPELINE,) if self._pipeline_output else ()) + tuple(extra_fields))
+        rows = {}
+        for f in fields:
+            a = d.get(f"field_{f}")
+            shape = (self.num_envs, self.device_field(f)[1])
+            if a is None or np.asarray(a).dtype != np.uint32 or np.asarray(a).shape != shape:
+                raise ValueError(f"the state_dict's field {f} must be uint32 {shape}")
+            rows[f] = np.ascontiguousarray(a)
+        self._before_launch()
+        for f, a in rows.items():
+            _lib.check(self._L.pp3_copy_field_from_host(self._h, f, a.ctypes.data_as(C.c_void_p), a.nbytes))
+        return self._issue(False)
 
     # ------------------------------------------------------------------ host API
     def _batch_keys(self, rng) -> Tuple[np.ndarray, bool]:

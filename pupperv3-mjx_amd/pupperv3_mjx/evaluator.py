@@ -167,6 +167,17 @@ class Evaluator:
         res.update(training_metrics or {})
         return res
 
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        """{"key": the key the next evaluation splits}: all an Evaluator carries from one evaluation to
+        the next (every evaluation resets its envs and its accumulator; the walltime is a timing)."""
+        return {"key": self._key.copy()}
+
+    def load_state_dict(self, d: Dict[str, np.ndarray]) -> None:
+        key = np.asarray(d["key"])
+        if key.dtype != np.uint32 or key.shape != (2,):
+            raise ValueError("the Evaluator's state_dict holds key: uint32 [2]")
+        self._key = np.array(key)
+
     def close(self) -> None:
         for b in (self._acc, self._out, self._actions) + (self._rows or ()):
             b.free()

@@ -151,6 +151,44 @@ def convert_value_params(params, activation: str, observation_history: int) -> D
     return {"observation_history": observation_history, "in_shape": [None, input_size], "layers": layers}
 
 
+METADATA_KEYS = ("action_scale", "kp", "kd", "default_pose", "joint_upper_limits", "joint_lower_limits", "use_imu",
+                 "observation_history", "maximum_pitch_command", "maximum_roll_command")
+
+
+def zero_network_dicts(observation_size: int, policy_hidden_layer_sizes, value_hidden_layer_sizes,
+                       activation: str = "elu", min_std: float = 0.001, var_scale: float = 1.0, **metadata):
+    """(policy dict, value dict) in the forms of `convert_training_params` and `convert_value_params`
+    for Brax's make_ppo_networks shapes, un-folded and with all-zero f32 weights: the policy
+    observation_size -> hidden.. -> 24 (the normal_tanh head), the value net observation_size ->
+    hidden.. -> 1, hidden layers `activation`, last layers linear.  For ppo.make_learner, which
+    fills the weights on the device.  `metadata`: none, or all of METADATA_KEYS (convert_params'
+    arguments of those names: what the deployment JSON carries beside "layers")."""
+    if activation.lower() not in ACTIVATIONS:
+        raise ValueError(f"unsupported activation {activation!r} (device: {sorted(ACTIVATIONS)})")
+    if metadata and set(metadata) != set(METADATA_KEYS):
+        raise ValueError(f"the export metadata is none or all of {METADATA_KEYS}; got {sorted(metadata)}")
+
+    def layers(widths):
+        out, k = [], int(observation_size)
+        for i, m in enumerate(widths):
+            out.append({"type": "dense", "activation": activation if i < len(widths) - 1 else "linear",
+                        "shape": [None, int(m)],
+                        "weights": [np.zeros((k, int(m)), np.float32), np.zeros(int(m), np.float32)]})
+            k = int(m)
+        return out
+
+    pl = layers(tuple(policy_hidden_layer_sizes) + (24,))
+    if metadata:
+        policy = _policy_dict(pl, int(observation_size), *(metadata[k] for k in METADATA_KEYS))
+    else:
+        policy = {"in_shape": [None, int(observation_size)], "layers": pl}
+    policy["distribution"] = {"type": "normal_tanh", "min_std": float(min_std), "var_scale": float(var_scale)}
+    value = {"in_shape": [None, int(observation_size)], "layers": layers(tuple(value_hidden_layer_sizes) + (1,))}
+    if "observation_history" in metadata:
+        value["observation_history"] = metadata["observation_history"]
+    return policy, value
+
+
 def _softplus(x):
     return np.maximum(x, 0) + np.log1p(np.exp(-np.abs(x)))
 

@@ -44,12 +44,27 @@ callable of the iteration index.
     actor, critic, metrics = ppo.train(learner, wrap(env, 1000), wrap(eval_env, 1000), num_timesteps=10_000_000,
                                        episode_length=1000, num_evals=10, key=key, progress_fn=progress)
 
+Initial parameters: `make_learner(key, observation_size, ...)` builds a learner of Brax's
+make_ppo_networks shapes and draws lecun_uniform kernels and zero biases on the device
+(`PPOLearner.init_params` = pp3_learner_init_params; `init_params` is one net in numpy, the same
+bits).  Ranks that pass the same key hold identical parameters without a broadcast.
+
+Checkpoints: `PPOLearner.state_dict` / `load_state_dict` (parameters, Adam's moments, t, the
+normaliser), the same pair on PupperV3Env, wrappers.wrap's env and the Evaluator, one atomic .npz of
+plain arrays by `save_checkpoint` / `load_checkpoint`, and `train(checkpoint_path=, restore=)`: a run
+interrupted at a checkpoint and resumed on fresh objects ends with the bits of the uninterrupted run.
+
+    learner = ppo.make_learner(key, env.observation_size, max_rows=(K + 1) * N)
+    ppo.train(learner, env, eval_env, ..., checkpoint_path=lambda steps: f"ck_{steps}.npz")
+    ppo.train(learner2, env2, eval_env2, ..., restore="ck_36000000.npz")      # after a crash
+
 Not here (follow-ups): bf16 / mixed precision, a cross-rank reduce of the evaluation metrics.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 import time
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
@@ -372,6 +387,98 @@ class PPOLearner:
                                           C.c_void_p(stream) if stream else None))
         self.t = t
 
+    # ---- initialisation and checkpoints -------------------------------------------------------
+    def _drop_noise(self) -> None:
+        """Forgets the cached entropy-noise draws (the next loss_and_grad draws again)."""
+        self._dev_eps = None
+        if self._eps is not None:
+            self._eps[1].free()
+            self._eps = None
+
+    def init_params(self, key, partitionable: Optional[bool] = None) -> None:
+        """Brax's initial networks drawn on the device from `key` (pp3_learner_init_params: lecun_uniform
+        kernels, zero biases; the key schedule and the numpy restatement: `ppo.init_params`), on the
+        stream of the env the last call ran on (else the default stream).  The gradients and both Adam
+        moments become zero, t = 0, a running_statistics normaliser returns to Brax's initial state
+        (count 0, mean 0, summed_variance 0, std 1) and the cached noise draw is dropped.  Handles made
+        earlier keep their weights until `sync`.  partitionable: by default that env's (else jax 0.5's
+        layout).  Ranks that pass the same key hold the same bits; no broadcast is needed."""
+        if partitionable is None:
+            partitionable = self._env._partitionable if self._env is not None else True
+        k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+        self._check(self._L.pp3_learner_init_params(self._h, _vp(k), int(bool(partitionable)), self._stream()))
+        self.t = 0
+        if self.running_statistics:
+            self._wait()
+            self._norm.upload(np.stack([np.zeros(self.in_dim, np.float32), np.ones(self.in_dim, np.float32),
+                                        np.zeros(self.in_dim, np.float32)]))
+            self._count = 0
+        self._drop_noise()
+
+    def _describe(self) -> Dict[str, np.ndarray]:
+        """What a state_dict's blobs depend on (compared at load)."""
+        (pin, pout, pact), (_, vout, vact) = self._shapes
+        return {"in_dim": np.asarray(pin, np.int64),
+                "policy_widths": np.asarray(pout, np.int32), "policy_activations": np.asarray(pact, np.int32),
+                "value_widths": np.asarray(vout, np.int32), "value_activations": np.asarray(vact, np.int32),
+                "min_std": np.asarray(self.distribution["min_std"], np.float32),
+                "var_scale": np.asarray(self.distribution["var_scale"], np.float32),
+                "running_statistics": np.asarray(self.running_statistics, np.bool_),
+                "has_normalizer": np.asarray(self._norm is not None, np.bool_)}
+
+    _BLOBS = tuple((f"{name}_{what}", net, which) for net, name in ((0, "policy"), (1, "value"))
+                   for which, what in ((0, "params"), (2, "m"), (3, "v")))
+
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        """Everything an iteration reads that an earlier one wrote, as plain arrays (waits for the
+        stream): per net the parameter blob and Adam's m and v (flat f32, the layout of `buffer`), t,
+        and with a normaliser its rows mean | std | summed_variance [3][in_dim] and the count; beside
+        them the shapes and flags `load_state_dict` compares.  Not state, because train_iteration
+        rewrites each before it reads it: the gradients (every loss_and_grad stores all of both blobs
+        before the clip or Adam reads them), the workspaces, the metrics, the env index (set by each
+        shuffled pass before the indexed loss reads it; unshuffled passes never read it) and the noise
+        buffer (drawn at an iteration's first loss_and_grad, the cache being dropped at load)."""
+        d = self._describe()
+        for name, net, which in self._BLOBS:
+            d[name] = self._download(net, which)
+        d["t"] = np.asarray(self.t, np.int64)
+        if self._norm is not None:
+            ns = self.normalizer_state()
+            d["normalizer"] = np.stack([ns["mean"], ns["std"], ns["summed_variance"]])
+            d["count"] = np.asarray(ns["count"], np.int64)
+        return d
+
+    def load_state_dict(self, d: Dict[str, np.ndarray]) -> None:
+        """Puts a `state_dict` back: ValueError, with nothing touched, when a shape, an activation,
+        min_std, var_scale, running_statistics or the presence of a normaliser differs from this
+        learner's or an array is missing or misshapen; else the blobs are uploaded behind the stream's
+        queued work, t and the count set, and the cached noise draw dropped.  Handles made earlier
+        keep their weights until `sync` (make_policies after a load returns loaded ones)."""
+        for k, v in self._describe().items():
+            if k not in d or not np.array_equal(np.asarray(d[k]), v):
+                raise ValueError(f"the state_dict is of another learner: {k} is {d.get(k)}, this learner's is {v}")
+        want = {name: (self.buffer(net, which)[1],) for name, net, which in self._BLOBS}
+        if self._norm is not None:
+            want["normalizer"] = (3, self.in_dim)
+        arrays = {}
+        for name, shape in want.items():
+            a = np.asarray(d[name]) if name in d else None
+            if a is None or a.dtype != np.float32 or a.shape != shape:
+                raise ValueError(f"the state_dict's {name} must be float32 {shape}")
+            arrays[name] = np.ascontiguousarray(a)
+        for name in ("t",) + (("count",) if self._norm is not None else ()):
+            if name not in d or int(d[name]) < 0:
+                raise ValueError(f"the state_dict lacks {name}")
+        self._wait()
+        for name, net, which in self._BLOBS:
+            a = arrays[name]
+            _lib.check(self._L.pp3_memcpy_h2d(C.c_void_p(self.buffer(net, which)[0]), _vp(a), a.nbytes))
+        if self._norm is not None:
+            self._norm.upload(arrays["normalizer"])
+            self._count = int(d["count"])
+        self.t = int(d["t"])
+        self._drop_noise()
+
     def make_policies(self) -> Tuple[DevicePolicy, DevicePolicy]:
         """(actor, critic) handles of the networks' shapes, loaded with the current parameters."""
         actor, critic = DevicePolicy(self._dicts[0], self.device), DevicePolicy(self._dicts[1], self.device)
@@ -477,6 +584,116 @@ class PPOLearner:
             pass
 
 
+def init_params(key, in_dim: int, hidden, out: int, partitionable: bool = True) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """One network's initial [(kernel [in][out], bias [out]), ...] from its net key, in numpy: the
+    contract above pp3_learner_init_params in include/pupper_hip.h, which the device entry equals bit
+    for bit.  Layers in_dim -> hidden.. -> out; for layer l in order `key, k_l = rng.split(key)`, the
+    kernel rng.uniform(k_l, (fan_in, width), -1, 1) * s with s = sqrt(3 * (1 / fan_in)) in float32
+    (jax's lecun_uniform: variance 1 / fan_in), the bias zero.  A learner's two net keys are
+    `k_policy, k_value = rng.split(key)` of the key given to PPOLearner.init_params / make_learner.
+    The schedule is this library's own: flax folds module paths into the key, which cannot be
+    pinned here, so the distribution is Brax's and the stream behind it is not."""
+    k_net = np.asarray(key, dtype=np.uint32).reshape(2)
+    layers, fan_in = [], int(in_dim)
+    for width in tuple(int(m) for m in hidden) + (int(out),):
+        k_net, k_l = rng.split(k_net, 2, partitionable)
+        s = np.sqrt(np.float32(3.0) * (np.float32(1.0) / np.float32(fan_in)))
+        u = rng.uniform(k_l, (fan_in, width), -1.0, 1.0, partitionable)
+        layers.append(((u * np.float32(s)).astype(np.float32), np.zeros(width, np.float32)))
+        fan_in = width
+    return layers
+
+
+def make_learner(key, observation_size: int, policy_hidden_layer_sizes=(256, 128, 128),
+                 value_hidden_layer_sizes=(256, 128, 128), activation: str = "elu", min_std: float = 0.001,
+                 var_scale: float = 1.0, running_statistics: bool = True, max_rows: int = 21 * 4096, device: int = 0,
+                 **export_metadata) -> PPOLearner:
+    """A PPOLearner of Brax's make_ppo_networks shapes (the policy's last layer the 24-column
+    normal_tanh head, the value net's one column, both un-folded) with Brax's initial parameters
+    drawn on the device from `key` (PPOLearner.init_params, in jax 0.5's counter layout; for an env
+    of rng_partitionable=False call `init_params(key, False)` again).  export_metadata: none, or all of
+    export.METADATA_KEYS (convert_params' arguments: action scale, kp, kd, poses, limits, use_imu,
+    observation_history, pitch / roll maxima), kept beside the layers so that `deterministic_policy()`
+    and a JSON export of it carry them."""
+    from .export import zero_network_dicts
+    pol, val = zero_network_dicts(observation_size, policy_hidden_layer_sizes, value_hidden_layer_sizes, activation,
+                                  min_std, var_scale, **export_metadata)
+    learner = PPOLearner(pol, val, device=device, max_rows=max_rows, running_statistics=running_statistics)
+    learner.init_params(key)
+    return learner
+
+
+# ---- checkpoints ------------------------------------------------------------------------------
+CHECKPOINT_PARTS = ("learner", "env", "evaluator", "loop")
+
+
+def _part(obj) -> Dict[str, np.ndarray]:
+    """A checkpoint part: an object's state_dict(), or a mapping of arrays as it is."""
+    d = obj.state_dict() if hasattr(obj, "state_dict") else obj
+    out = {}
+    for k, v in d.items():
+        a = np.asarray(v)
+        if a.dtype == object or "/" in k:
+            raise ValueError(f"a checkpoint holds plain arrays under names without '/': {k!r}")
+        out[k] = a
+    return out
+
+
+def save_checkpoint(path, learner, env, state=None, evaluator=None, loop: Optional[Dict[str, Any]] = None) -> None:
+    """One .npz of plain arrays (scalars as 0-d arrays; no pickled object) under "<part>/<name>": the
+    state_dict() of the learner, of the training env (a wrappers.wrap'ped env or a PupperV3Env) and
+    of the evaluator, and `loop`, what `train` needs to continue (its key chain, the iteration and
+    epoch indices, the walltime, the schedule).  `state`: the env State to save; the device usually
+    holds it, an edited one is written back first as a step would.  Each of learner / env / evaluator
+    may also be a mapping of arrays.  The file is written under a temporary name in the same
+    directory and renamed over `path` (os.replace), so a killed job leaves the last complete
+    checkpoint, never a partial one."""
+    if state is not None and hasattr(env, "state_dict"):
+        base = _base(env)
+        if not base.holds(state):
+            if env is not base:
+                env._prepare(state)
+            base._write_state(state)
+    arrays = {}
+    for name, obj in zip(CHECKPOINT_PARTS, (learner, env, evaluator, loop)):
+        if obj is not None:
+            arrays.update({f"{name}/{k}": v for k, v in _part(obj).items()})
+    path = os.fspath(path)
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        with open(tmp, "wb") as f:
+            np.savez(f, **arrays)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def load_checkpoint(path) -> Dict[str, Dict[str, np.ndarray]]:
+    """{"learner" | "env" | "evaluator" | "loop": {name: array}} of a save_checkpoint file (the parts
+    it was given), read with allow_pickle=False; each part is what that object's load_state_dict
+    takes."""
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    with np.load(os.fspath(path), allow_pickle=False) as z:
+        for full in z.files:
+            part, _, name = full.partition("/")
+            if part not in CHECKPOINT_PARTS or not name:
+                raise ValueError(f"{path}: not a checkpoint of this library (entry {full!r})")
+            out.setdefault(part, {})[name] = z[full]
+    return out
+
+
+def _loop_schedule(sched: Dict[str, Any], unroll_length: int, num_minibatches: int,
+                   num_updates_per_batch: int) -> Dict[str, np.ndarray]:
+    d = {f"schedule_{k}": np.asarray(v, dtype=np.int64) for k, v in sched.items()}
+    d.update(unroll_length=np.asarray(unroll_length, np.int64), num_minibatches=np.asarray(num_minibatches, np.int64),
+             num_updates_per_batch=np.asarray(num_updates_per_batch, np.int64))
+    return d
+
+
 def eval_schedule(num_timesteps: int, num_envs: int, unroll_length: int, action_repeat: int = 1,
                   num_evals: int = 1) -> Dict[str, Any]:
     """Brax ppo.train's schedule ([ext] brax 0.12.1 training/agents/ppo/train.py, from memory), with one
@@ -501,7 +718,7 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
           deterministic_eval: bool = False, key, progress_fn: Optional[Callable[[int, Dict[str, Any]], None]] = None,
           policy_params_fn: Optional[Callable[..., None]] = None, shuffle: bool = True,
           max_grad_norm: Optional[float] = None, normalize_observations: bool = False, device_rng: bool = True,
-          comm=None, **hparams):
+          comm=None, checkpoint_path=None, restore=None, **hparams):
     """Brax's ppo.train loop around `learner.train_iteration` (the schedule: eval_schedule).  `env`
     and `eval_env` are `wrappers.wrap`ped envs of this `episode_length` / `action_repeat`; `eval_env`
     may also be a constructed `evaluator.Evaluator` (e.g. one on the reward path), or None to train
@@ -516,7 +733,23 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
     `learner.deterministic_policy()`, rebuilt from the parameters at every evaluation; otherwise it
     samples from the actor.  normalize_observations: train_iteration(update_normalizer=True), which
     needs PPOLearner(running_statistics=True).  comm: every rank trains on its own shard with its own
-    key and evaluates its own eval env; the evaluation metrics are not reduced across ranks."""
+    key and evaluates its own eval env; the evaluation metrics are not reduced across ranks.
+
+    checkpoint_path (a path, or a callable of num_steps returning one): after every evaluation --
+    without an evaluator at the same epoch boundaries -- and after progress_fn and policy_params_fn,
+    `save_checkpoint` writes the learner, the training env with the state the next epoch starts from,
+    the evaluator's key and the loop (k_train, the iteration and epoch indices, the walltime, the
+    schedule).  restore (such a file's path, or `load_checkpoint`'s dict): instead of resetting the
+    envs and evaluating once, the learner, the env and the evaluator are loaded and training continues
+    at the saved epoch with the saved k_train and iteration index (a callable learning_rate sees the
+    continuing index); a run interrupted at a checkpoint and resumed, in a fresh process on fresh
+    objects built with the same arguments, ends with the bits of the uninterrupted run.  ValueError
+    before anything is loaded when the saved schedule (eval_schedule's dict, unroll_length,
+    num_minibatches, num_updates_per_batch) is not the one these arguments give; `key` is not read
+    for the continuation.  Under comm every rank saves and restores its own file (its env shard and
+    keys differ, the learner part is identical): the caller puts the rank in the path; no
+    collective is added.  Domain randomisation and terrain are configuration the caller sets as at
+    first."""
     from .evaluator import Evaluator
     base = _base(env)
     n, part = base.num_envs, base._partitionable
@@ -525,9 +758,27 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
                                                                                       int(action_repeat)):
             raise ValueError("train needs wrappers.wrap'ped envs of the given episode_length and action_repeat")
     sched = eval_schedule(num_timesteps, n, unroll_length, action_repeat, num_evals)
+    loop_sched = _loop_schedule(sched, unroll_length, num_minibatches, num_updates_per_batch)
+    ck = None
+    if restore is not None:
+        ck = restore if isinstance(restore, dict) else load_checkpoint(restore)
+        saved = ck.get("loop")
+        if saved is None or any(k not in saved for k in ("k_train", "iteration", "epoch", "walltime")):
+            raise ValueError("restore: the checkpoint has no training loop part (save_checkpoint(loop=...))")
+        for k, v in loop_sched.items():
+            if k not in saved or not np.array_equal(np.asarray(saved[k]), v):
+                raise ValueError(f"restore: the checkpoint was written under another schedule: {k} is "
+                                 f"{saved.get(k)}, these arguments give {v}")
+        if "learner" not in ck or "env" not in ck or (eval_env is not None and "evaluator" not in ck):
+            raise ValueError("restore: the checkpoint lacks the learner, the env or the evaluator")
     k_train, k_env, k_eval = rng.split(np.asarray(key, dtype=np.uint32).reshape(2), 3, part)
-    state = env.reset(rng.split(k_env, n, part))
-    actor, critic = learner.make_policies()
+    if ck is None:
+        state = env.reset(rng.split(k_env, n, part))
+        actor, critic = learner.make_policies()
+    else:
+        learner.load_state_dict(ck["learner"])
+        actor, critic = learner.make_policies()
+        state = env.load_state_dict(ck["env"])  # (it ends with a device-wide wait: the handles are loaded)
     if eval_env is None:
         evaluator = None
     elif isinstance(eval_env, Evaluator):
@@ -537,6 +788,18 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
                               deterministic=deterministic_eval)
     metrics: Dict[str, Any] = {}
     walltime = 0.0
+    it, epoch0 = 0, 0
+    if ck is not None:
+        if evaluator is not None:
+            evaluator.load_state_dict(ck["evaluator"])
+        k_train = np.array(np.asarray(ck["loop"]["k_train"], dtype=np.uint32).reshape(2))
+        it, epoch0, walltime = int(ck["loop"]["iteration"]), int(ck["loop"]["epoch"]), float(ck["loop"]["walltime"])
+
+    def checkpoint(num_steps: int, next_epoch: int) -> None:
+        path = checkpoint_path(num_steps) if callable(checkpoint_path) else checkpoint_path
+        loop = dict(loop_sched, k_train=np.asarray(k_train, dtype=np.uint32), iteration=np.asarray(it, np.int64),
+                    epoch=np.asarray(next_epoch, np.int64), walltime=np.asarray(walltime, np.float64))
+        save_checkpoint(path, learner, env, state, evaluator, loop)
 
     def evaluate(num_steps: int, training_metrics: Dict[str, Any]) -> Dict[str, Any]:
         pol = learner.deterministic_policy() if evaluator.deterministic else actor
@@ -551,10 +814,11 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
             policy_params_fn(num_steps, learner.params(), learner.normalizer_state() if learner._norm is not None else None)
         return m
 
-    if evaluator is not None and sched["eval_before_training"]:
+    if ck is None and evaluator is not None and sched["eval_before_training"]:
         metrics = evaluate(0, {})
-    it = 0
-    for epoch in range(sched["num_evals_after_init"]):
+        if checkpoint_path is not None:
+            checkpoint(0, 0)
+    for epoch in range(epoch0, sched["num_evals_after_init"]):
         t0 = time.time()
         for _ in range(sched["iterations_per_epoch"]):
             k_train, k_it = rng.split(k_train, 2, part)
@@ -571,6 +835,8 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
         metrics["training/walltime"] = walltime
         if evaluator is not None:
             metrics = evaluate(it * sched["steps_per_iteration"], metrics)
+        if checkpoint_path is not None:
+            checkpoint(it * sched["steps_per_iteration"], epoch + 1)
     if evaluator is not None and evaluator is not eval_env:
         evaluator.close()
     return actor, critic, metrics

@@ -81,8 +81,8 @@ class AutoResetEpisodeEnv:
                 "first_pipeline_state": None if first_ps is None else dict(first_ps),
                 "first_obs": first_obs}
 
-    def reset(self, rng) -> State:
-        st = self.env.reset(rng)
+    def _read_first(self, st: State) -> State:
+        """The host copies of the first state / obs from the device fields, attached to `st`."""
         sq = (lambda v: v[0]) if np.ndim(st.reward) == 0 else (lambda v: v)
         first = self.env._get(_abi.F_FIRST_STATE)
         fobs = self.env._get(_abi.F_FIRST_OBS)
@@ -91,6 +91,25 @@ class AutoResetEpisodeEnv:
         self._first_obs = sq(fobs.copy())
         st.__dict__["_capture"] = (self._first_ps, self._first_obs)  # (issued before they were read)
         return st
+
+    def reset(self, rng) -> State:
+        return self._read_first(self.env.reset(rng))
+
+    _CHECKPOINT_FIELDS = (_abi.F_EPISODE, _abi.F_FIRST_STATE, _abi.F_FIRST_OBS)
+
+    def state_dict(self):
+        """PupperV3Env.state_dict with the wrapper's device fields: the episode record (steps,
+        truncation, the episode's reward sum and length) and the first state and obs the auto-reset
+        restores; episode_length and action_repeat join what must match at load."""
+        return self.env.state_dict(self._CHECKPOINT_FIELDS, episode_length=self.episode_length,
+                                   action_repeat=self.action_repeat)
+
+    def load_state_dict(self, d) -> State:
+        """PupperV3Env.load_state_dict for a dict of `state_dict()`; the host copies of the first
+        state / obs are read back from the uploaded fields, as `reset` reads them."""
+        st = self.env.load_state_dict(d, self._CHECKPOINT_FIELDS, episode_length=self.episode_length,
+                                      action_repeat=self.action_repeat)
+        return self._read_first(st)
 
     def step(self, state: State, action) -> State:
         self._prepare(state)
