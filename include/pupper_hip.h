@@ -637,6 +637,76 @@ int pp3_eval_accumulate_rows(int32_t device, int32_t nsteps, int32_t n, int64_t 
                              const float* done, int32_t step0, int32_t action_repeat, float* acc, void* stream);
 int pp3_eval_reduce(int32_t device, int32_t n, const float* acc, float* out42, void* stream);
 
+/* ---- PPO metrics: rank-ordered sums, the evaluation reduce over ranks, training episode statistics
+ * (additive; PP3_ABI_VERSION stays 2) ----
+ * Free functions on raw device pointers in pp3_gae's style: f32, every operation rounded on its own
+ * (no fused multiply-add), no atomics (a call repeats bit for bit), errors through
+ * pp3_ppo_last_error(), PP3_ERR_ARG before any launch with the outputs untouched.  None of them makes
+ * a collective: a sum over ranks is pp3_comm_allgather_f32 into [world][count], then
+ * pp3_sum_gathered_f32 (pupperv3_mjx sharding.Comm.sum_ranks_device), the same bits on every rank.
+ *
+ * pp3_sum_gathered_f32: out[i] = ((g_0[i] + g_1[i]) + g_2[i]) + .. over the rows g_r = gathered[r]
+ * of gathered f32[world][count], in rank order starting from rank 0's value (world 1: a copy).
+ * PP3_ERR_ARG: a null pointer, world outside 1 .. PP3_LEARN_MAX_WORLD, count outside 1 .. 2^30, out
+ * overlapping gathered.
+ *
+ * pp3_eval_reduce cut at the two places where the sum over ranks goes in.  acc is a pp3_eval_*
+ * accumulator of this rank's n eval envs; reduced column k is metrics column k for k < 20 and
+ * episode_steps for k = 20.
+ * pp3_eval_column_sums, mean21 NULL: out22[k] = the sum of reduced column k over the n envs in
+ * pp3_eval_reduce's order (one 1024-lane workgroup; lane i adds envs i, i + 1024, .. ascending from 0,
+ * then the binary tree), k < 21; out22[21] = (float)n.  mean21 given (f32[21], device): out22[k] = the
+ * sum of (x - mean21[k]) * (x - mean21[k]) in the same order; out22[21] = (float)n.
+ * pp3_eval_finish, which 0: out42[k] = sums22[k] / sums22[21]; which 1: out42[21 + k] =
+ * sqrt(sums22[k] / sums22[21]); k < 21, the quotient and the root those of pp3_eval_reduce (one
+ * residual step each).  The other half of out42 is left alone.
+ * The chain: column_sums(NULL) -> sum over ranks -> finish(0) -> column_sums(out42) -> sum over
+ * ranks -> finish(1).  On one rank's data alone (world 1) it equals pp3_eval_reduce bit for bit.
+ * Over ranks the mean and the std weigh every eval env of the job equally, whatever its rank's
+ * shard size: both sums and the env count are summed, so ragged shards are exact.  This is not
+ * Brax's pmean of per-device means, which weighs every device equally; the two agree when all
+ * shards have the same size.  The env count must stay below 2^24 (exact in f32).
+ * PP3_ERR_ARG: a null pointer other than mean21, n < 1, which not 0 or 1, an output overlapping an
+ * input.
+ *
+ * Training episode statistics: EpisodeWrapper's episode_metrics (sum_reward, length) at the done steps
+ * of a collected batch ([ext] brax 0.12.1 envs/wrappers/training.py and ppo.train's
+ * log_training_metrics, restated from memory; what is written here is the contract).  A fused K-step
+ * rollout leaves only the record's last value in PP3_F_EPISODE; these rebuild the record at every
+ * step from the batch's rows with the step kernel's own arithmetic.
+ * pp3_episode_stats_begin, queued before the rollout: carry f32[3][n] (row r of env i at carry[r * n +
+ * i]) from the env's fields: ret = word PP3_EP_SUM_REWARD and len = word PP3_EP_LENGTH of episode
+ * [n][episode_stride] (PP3_F_EPISODE), pd = done [n] (PP3_F_DONE).
+ * pp3_episode_stats_rows, queued after the rollout, on its reward / done / truncation rows
+ * [nsteps][n] (row stride row_stride floats; truncation NULL is read as all 0).  Per env i, for
+ * t = 0 .. nsteps-1 in order, with cnt = sret = slen = strunc = 0 before the loop in every call:
+ *     keep = 1 - pd
+ *     ret  = (ret + reward[t][i]) * keep
+ *     len  = (len + (float)action_repeat) * keep
+ *     if done[t][i] != 0:
+ *         cnt = cnt + 1;  sret = sret + ret;  slen = slen + len;  strunc = strunc + truncation[t][i]
+ *     pd   = done[t][i]
+ * This is the step kernel's line for the record, so the step after a done step contributes nothing
+ * (as in Brax, whose record restarts one step late), and carry (written back: ret, len, pd) equals
+ * the env's PP3_F_EPISODE words and PP3_F_DONE after the rollout bit for bit.  part f32[4][n] is the
+ * caller's workspace and receives (cnt, sret, slen, strunc) per env; out4 f32[4] = (episodes, sum of
+ * returns, sum of lengths, truncated episodes): each row of part summed over the envs in
+ * pp3_eval_reduce's order.  Two kernels: the chain, one lane per env with the next rows' loads in
+ * flight ahead of it, then the one-workgroup sum.
+ * PP3_ERR_ARG: a null pointer other than truncation, n < 1, nsteps < 1, row_stride < n,
+ * action_repeat < 1, episode_stride < PP3_EP_STRIDE, nsteps * n >= 2^24 (the count stays exact in
+ * f32), carry / part / out4 overlapping an input or each other. */
+int pp3_sum_gathered_f32(int32_t device, const float* gathered, int32_t world, int64_t count, float* out,
+                         void* stream);
+int pp3_eval_column_sums(int32_t device, int32_t n, const float* acc, const float* mean21, float* out22,
+                         void* stream);
+int pp3_eval_finish(int32_t device, const float* sums22, int32_t which, float* out42, void* stream);
+int pp3_episode_stats_begin(int32_t device, int32_t n, const float* episode, int64_t episode_stride,
+                            const float* done, float* carry, void* stream);
+int pp3_episode_stats_rows(int32_t device, int32_t nsteps, int32_t n, int64_t row_stride, const float* reward,
+                           const float* done, const float* truncation, int32_t action_repeat, float* carry,
+                           float* part, float* out4, void* stream);
+
 /* ---- PPO learner: loss gradients, Adam, weight reload (additive; PP3_ABI_VERSION stays 2) ----
  * One PPO iteration on the env's stream with no host round trip: collect, per minibatch loss +
  * gradient + Adam, reload the actor and the critic, collect again (csrc/pp3_learn.hip).  All f32.

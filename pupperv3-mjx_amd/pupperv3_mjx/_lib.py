@@ -152,6 +152,15 @@ def load() -> C.CDLL:
         L.pp3_eval_reduce.argtypes = [i32, i32, vp, vp, vp]
         for name in ("pp3_eval_reset", "pp3_eval_accumulate", "pp3_eval_accumulate_rows", "pp3_eval_reduce"):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, "pp3_episode_stats_rows"):  # (the PPO metrics; absent from earlier builds run in kernel A/B)
+        L.pp3_sum_gathered_f32.argtypes = [i32, vp, i32, i64, vp, vp]
+        L.pp3_eval_column_sums.argtypes = [i32, i32, vp, vp, vp, vp]
+        L.pp3_eval_finish.argtypes = [i32, vp, i32, vp, vp]
+        L.pp3_episode_stats_begin.argtypes = [i32, i32, vp, i64, vp, vp, vp]
+        L.pp3_episode_stats_rows.argtypes = [i32, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]
+        for name in ("pp3_sum_gathered_f32", "pp3_eval_column_sums", "pp3_eval_finish", "pp3_episode_stats_begin",
+                     "pp3_episode_stats_rows"):
+            getattr(L, name).restype = C.c_int
     L.pp3_stream.argtypes = [vp]
     L.pp3_stream.restype = vp
     if hasattr(L, "pp3_event_create"):  # (absent from pre-round-5 builds run in kernel A/B: no host-API step there)
@@ -221,6 +230,8 @@ EXPORTED_SYMBOLS = (
     "pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample", "pp3_rollout_policy_sample_timed",
     "pp3_set_truncation_trajectory", "pp3_gae", "pp3_ppo_last_error",
     "pp3_eval_reset", "pp3_eval_accumulate", "pp3_eval_accumulate_rows", "pp3_eval_reduce",
+    "pp3_sum_gathered_f32", "pp3_eval_column_sums", "pp3_eval_finish", "pp3_episode_stats_begin",
+    "pp3_episode_stats_rows",
     "pp3_learner_create", "pp3_learner_destroy", "pp3_learner_buffers", "pp3_ppo_loss_grad", "pp3_adam_step",
     "pp3_policy_load_params", "pp3_learn_last_error",
     "pp3_learner_normalizer_update", "pp3_learner_set_env_index", "pp3_ppo_loss_grad_indexed", "pp3_grad_clip",

@@ -1011,8 +1011,8 @@ class PupperV3Env:
         return self._issue(single), traj, k_out
 
     def collect_ppo(self, state: State, policy, value, nsteps: int, key, discount: float = 0.97,
-                    gae_lambda: float = 0.95,
-                    reward_scaling: float = 1.0) -> Tuple[State, Dict[str, np.ndarray], np.ndarray]:
+                    gae_lambda: float = 0.95, reward_scaling: float = 1.0,
+                    host_batch: bool = True) -> Tuple[State, Optional[Dict[str, np.ndarray]], np.ndarray]:
         """One PPO batch without the trajectory leaving the device between the env step and the
         targets: rollout_policy_sample's unroll (same returned state and key chain), the critic
         `value` (an `export.DevicePolicy` of `export.convert_value_params`, one output) on the K + 1
@@ -1025,7 +1025,12 @@ class PupperV3Env:
         step: row 0 is the observation the unroll started from), "truncation" [K, N], "value"
         [K, N], "bootstrap_value" [N] (the critic on the last next observation), "value_target"
         [K, N] (compute_gae's vs) and "advantage" [K, N]; single-env states: without the N axis.
-        The same arrays stay on the device: ppo_device_batch()."""
+        The same arrays stay on the device: ppo_device_batch().
+
+        host_batch=False (a learner on the same GPU, which reads ppo_device_batch()): nothing is
+        waited for and nothing of the batch is downloaded; returns (state, None, K_nsteps), the
+        same state and key.  The state's obs / reward / done are stored into a page-locked block
+        behind the batch's launches and wait for them when first read, as a step()'s do."""
         self._flush()
         single = _single_of(state)
         n, D, K = self.num_envs, self.observation_size, int(nsteps)
@@ -1066,6 +1071,15 @@ class PupperV3Env:
             "log_prob": (sbuf[1].ptr.value, (K, n)), "reward": (rew, (K, n)), "done": (done, (K, n)),
             "truncation": (tb.ptr.value, (K, n)), "value": (val_all, (K, n)),
             "bootstrap_value": (val_all + 4 * K * n, (n,)), "value_target": (vs, (K, n)), "advantage": (adv, (K, n))}
+        if not host_batch:
+            # obs | reward | done of the state by one kernel into a page-locked block, then the
+            # completion event of a ring slot: the returned state waits for it on first read
+            lease = _lib.PinnedBlock.take(4 * n * (D + 2), self._pin_pool)
+            _lib.check(self._L.pp3_outputs_to_host(self._h, C.c_void_p(lease.ptr.value)))
+            slot = self._act_ring[self._act_i]
+            self._act_i = (self._act_i + 1) % len(self._act_ring)
+            slot.record()
+            return self._issue(single, lease, slot), None, k_out
         self.synchronize()
         host = {"obs_all": np.empty((K + 1, n, D), np.float32), "val_all": np.empty((K + 1, n), np.float32)}
         for name, ptr in (("obs_all", obs_all), ("val_all", val_all)):

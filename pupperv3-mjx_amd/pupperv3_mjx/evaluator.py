@@ -22,6 +22,14 @@ what both compute:
 `deterministic=True` needs a deployment policy (12 outputs, tanh of the mean: `export.convert_params`,
 `PPOLearner.deterministic_policy`); `deterministic=False` samples from a training policy
 (`export.convert_training_params`, the learner's actor) with `generate_unroll`'s key chain.
+
+Across ranks (`comm`, a sharding.Comm; every rank evaluates its own eval env shard and makes the same
+calls): the mean / std keys are over the eval envs of all ranks.  pp3_eval_reduce is cut where the sums
+over ranks go in (pp3_eval_column_sums -> Comm.sum_ranks_device -> pp3_eval_finish, once for the means
+and once for the squared deviations: two all-gathers of 22 floats, summed in rank order, the same bits
+on every rank), still with one host wait.  Every env of the job weighs the same, so ragged shards are
+exact; Brax's pmean of per-device means weighs the devices equally instead (the same when the shards
+are equal).  `eval/sps` counts all ranks' envs; aggregate_episodes=False stays this rank's columns.
 """
 from __future__ import annotations
 
@@ -40,10 +48,12 @@ METRIC_NAMES = ("total_dist",) + _abi.REWARD_NAMES + ("reward",)  # the accumula
 class Evaluator:
     """See the module docstring.  `eval_env`: a `wrappers.wrap`ped env that this object drives from
     now on (every evaluation resets it); `episode_length` and `action_repeat` must be the wrapper's.
-    `key`: a jax-style uint32[2]; every evaluation consumes one split of it."""
+    `key`: a jax-style uint32[2]; every evaluation consumes one split of it.  `comm`: the mean / std
+    keys cover all ranks' eval envs (module docstring); None: this process's envs, with the launches
+    of a build without it."""
 
     def __init__(self, eval_env, policy, episode_length: int, action_repeat: int = 1, key=None,
-                 deterministic: bool = True, metrics: bool = True, chunk: int = 50):
+                 deterministic: bool = True, metrics: bool = True, chunk: int = 50, comm=None):
         if not isinstance(eval_env, AutoResetEpisodeEnv):
             raise ValueError("the Evaluator needs a wrapped env (wrappers.wrap: EpisodeWrapper + AutoResetWrapper)")
         if (int(episode_length), int(action_repeat)) != (eval_env.episode_length, eval_env.action_repeat):
@@ -66,7 +76,9 @@ class Evaluator:
         n, dev = self.base.num_envs, self.base.device
         self.num_envs = n
         self._acc = _lib.DeviceBuffer(4 * _abi.EVAL_WORDS * n, dev)
-        self._out = _lib.DeviceBuffer(4 * 2 * _abi.EVAL_NOUT, dev)
+        self.comm = comm
+        # out42, then with comm the rank-summed 22 (downloaded with it: the global env count) and this rank's 22
+        self._out = _lib.DeviceBuffer(4 * (2 * _abi.EVAL_NOUT + (2 * _abi.EVAL_WORDS if comm is not None else 0)), dev)
         self._actions = _lib.DeviceBuffer(4 * self.chunk * n * _abi.NU, dev)
         self._rows = None if self.metrics else (_lib.DeviceBuffer(4 * self.chunk * n, dev),
                                                 _lib.DeviceBuffer(4 * self.chunk * n, dev))
@@ -139,12 +151,27 @@ class Evaluator:
         part = base._partitionable
         self._key, k = (np.array(x) for x in rng.split(self._key, 2, part))
         self._accumulate(policy, k)
-        self._check(L.pp3_eval_reduce(base.device, self.num_envs, self._acc.ptr, self._out.ptr,
-                                      C.c_void_p(L.pp3_stream(base._h))))
-        base.synchronize()  # the evaluation's one host wait
-        out = np.empty(2 * _abi.EVAL_NOUT, np.float32)
-        self._out.download(out)
-        mean, std = out[:_abi.EVAL_NOUT], out[_abi.EVAL_NOUT:]
+        stream = L.pp3_stream(base._h)
+        total_envs = self.num_envs
+        if self.comm is None:
+            self._check(L.pp3_eval_reduce(base.device, self.num_envs, self._acc.ptr, self._out.ptr, C.c_void_p(stream)))
+            base.synchronize()  # the evaluation's one host wait
+            out = np.empty(2 * _abi.EVAL_NOUT, np.float32)
+            self._out.download(out)
+        else:
+            out42 = self._out.ptr.value
+            total, local = out42 + 4 * 2 * _abi.EVAL_NOUT, out42 + 4 * (2 * _abi.EVAL_NOUT + _abi.EVAL_WORDS)
+            for which, mean in ((0, None), (1, C.c_void_p(out42))):
+                self._check(L.pp3_eval_column_sums(base.device, self.num_envs, self._acc.ptr, mean, C.c_void_p(local),
+                                                   C.c_void_p(stream)))
+                self.comm.sum_ranks_device(local, total, _abi.EVAL_WORDS, stream)
+                self._check(L.pp3_eval_finish(base.device, C.c_void_p(total), which, C.c_void_p(out42),
+                                              C.c_void_p(stream)))
+            base.synchronize()  # the evaluation's one host wait
+            out = np.empty(2 * _abi.EVAL_NOUT + _abi.EVAL_WORDS, np.float32)
+            self._out.download(out)
+            total_envs = int(out[-1])  # (the rank sum of the shard sizes, exact in f32)
+        mean, std = out[:_abi.EVAL_NOUT], out[_abi.EVAL_NOUT:2 * _abi.EVAL_NOUT]
         cols = range(_abi.EVAL_NCOL) if self.metrics else (_abi.EVAL_NCOL - 1,)
         res: Dict[str, Any] = {}
         if aggregate_episodes:
@@ -162,7 +189,7 @@ class Evaluator:
         dt = time.time() - t0
         self._walltime += dt
         res["eval/epoch_eval_time"] = dt
-        res["eval/sps"] = self.num_envs * self.unroll * self.action_repeat / dt
+        res["eval/sps"] = total_envs * self.unroll * self.action_repeat / dt
         res["eval/walltime"] = self._walltime
         res.update(training_metrics or {})
         return res

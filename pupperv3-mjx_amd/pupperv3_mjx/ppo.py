@@ -58,7 +58,17 @@ interrupted at a checkpoint and resumed on fresh objects ends with the bits of t
     ppo.train(learner, env, eval_env, ..., checkpoint_path=lambda steps: f"ck_{steps}.npz")
     ppo.train(learner2, env2, eval_env2, ..., restore="ck_36000000.npz")      # after a crash
 
-Not here (follow-ups): bf16 / mixed precision, a cross-rank reduce of the evaluation metrics.
+Training metrics: `EpisodeStats` rebuilds Brax's EpisodeWrapper record (sum_reward, length) at the done
+steps of every collected batch on the device (pp3_episode_stats_*), `train_iteration(episode_stats=)`
+feeds it and `train(log_training_metrics=True)` reports episode/sum_reward, episode/length,
+episode/truncated and episode/count at every epoch end: a learning curve between evaluations.  Brax
+averages a deque of the last 100 finished episodes there; this averages every episode that ended
+in the epoch.  Under `comm` the iteration's four sums go through the rank-ordered sum, so every rank
+reports the job's numbers; `train(reduce_eval_metrics=True)` does the same for the evaluation
+(`Evaluator(comm=)`).  train_iteration collects with `collect_ppo(host_batch=False)`: the batch is
+never downloaded, and the iteration's only host wait is the one behind its returned metrics.
+
+Not here (follow-ups): bf16 / mixed precision.
 """
 from __future__ import annotations
 
@@ -523,7 +533,7 @@ class PPOLearner:
     def train_iteration(self, env, state, key, device_policy: DevicePolicy, device_value: DevicePolicy, nsteps: int,
                         num_minibatches: int = 1, num_updates_per_batch: int = 1, lr: float = 3e-4,
                         shuffle: bool = False, max_grad_norm: Optional[float] = None, update_normalizer: bool = False,
-                        comm=None, device_rng: bool = False, **hparams):
+                        comm=None, device_rng: bool = False, episode_stats: Optional["EpisodeStats"] = None, **hparams):
         """One PPO iteration in Brax's training_step order: collect_ppo with the handles (the old
         parameters and statistics), update_normalizer: the running statistics, then
         num_updates_per_batch passes over num_minibatches minibatches (loss, gradient, max_grad_norm:
@@ -538,7 +548,11 @@ class PPOLearner:
         path's bit for bit, the noise agrees with it to erfinvf rounding (module docstring).
         comm (a sharding.Comm; every rank makes the same call on its own env shard with its own key,
         see the module docstring): the statistics take every rank's rows, allreduce_gradients runs
-        between the loss and the clip, and the metrics are the mean over ranks."""
+        between the loss and the clip, and the metrics are the mean over ranks.
+        episode_stats (an EpisodeStats): `begin` is queued before the collect and `add` after it (under
+        comm with the rank sum, so every rank accumulates the job's numbers); its 16 bytes are
+        downloaded behind the wait the returned metrics make.  The collect is
+        collect_ppo(host_batch=False): no batch download and no other host wait in the iteration."""
         base = _base(env)
         n = base.num_envs
         if n % num_minibatches:
@@ -546,7 +560,15 @@ class PPOLearner:
         B = n // num_minibatches
         k_collect, k_eps = rng.split(np.asarray(key, dtype=np.uint32).reshape(2), 2, base._partitionable)
         gae = {k: hparams[k] for k in ("discount", "gae_lambda", "reward_scaling") if k in hparams}
-        state, _, k_out = env.collect_ppo(state, device_policy, device_value, nsteps, k_collect, **gae)
+        if episode_stats is not None:
+            if not base.holds(state):  # an edited state: on the device first, as the collect would put it
+                if env is not base:
+                    env._prepare(state)
+                base._write_state(state)
+            episode_stats.begin(env)
+        state, _, k_out = env.collect_ppo(state, device_policy, device_value, nsteps, k_collect, host_batch=False, **gae)
+        if episode_stats is not None:
+            episode_stats.add(env, comm)
         if update_normalizer:
             self.update_normalizer(env, comm)
         k_perm = rng.split(k_eps, 2, base._partitionable)[1] if shuffle else None
@@ -566,7 +588,10 @@ class PPOLearner:
                     self.clip_gradients(max_grad_norm)
                 self.adam_step(lr)
         self.sync(device_policy, device_value)
-        return state, self.metrics(), k_out
+        metrics = self.metrics()
+        if episode_stats is not None:
+            episode_stats.fetch()  # (metrics() has waited for the stream)
+        return state, metrics, k_out
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -576,6 +601,142 @@ class PPOLearner:
             for b in (self._norm, self._metrics, self._gnorm, self._eps[1] if self._eps else None):
                 if b is not None:
                     b.free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EpisodeStats:
+    """Training episode statistics: Brax's EpisodeWrapper episode_metrics (sum_reward, length) and
+    the truncation flag at the done steps of collected batches (the contract: "Training episode
+    statistics" in include/pupper_hip.h).  Owns the device buffers carry [3][N], part [4][N] and out4
+    and the host accumulators.
+
+        stats = EpisodeStats()
+        stats.begin(env); env.collect_ppo(...); stats.add(env)      # per batch, all queued, no wait
+        count, sums = stats.read()                                    # waits, then downloads 16 bytes
+
+    `env`: a wrappers.wrap'ped env (ValueError otherwise), always the same one.  `begin` seeds the
+    carry from the env's episode record and done flags, so it must be queued after the state the
+    collect starts from is on the device and before the collect; `add` chains over the batch's
+    reward / done / truncation rows (`env.ppo_device_batch()`).  With `comm` (every rank calls) the
+    batch's four sums are summed over the ranks in rank order first.  Each batch's f32 (episodes,
+    sum of returns, sum of lengths, truncated episodes) is added to the host accumulators in batch
+    order: the count a Python int, the sums Python floats.  `read()` -> (count, {"sum_reward",
+    "length", "truncated"}); `reset()` empties the accumulators.  Nothing here is training state:
+    the carry is re-seeded from the env at every `begin`."""
+
+    def __init__(self):
+        self._L = _lib.load()
+        self._bufs = None  # (n, device, carry, part, out4 | its rank sum)
+        self._env = None
+        self._pending = False  # an add() whose out4 has not been downloaded yet
+        self._src = 0          # byte offset of the numbers to download: out4, or its rank sum behind it
+        self.last = None       # the last downloaded batch's four f32
+        self.reset()
+
+    def reset(self) -> None:
+        self.count, self.sum_reward, self.length, self.truncated = 0, 0.0, 0.0, 0.0
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise _lib.PupperHipError(f"pupper_hip error {rc}: {self._L.pp3_ppo_last_error().decode(errors='replace')}")
+
+    def _buffers(self, env):
+        base = getattr(env, "env", None)
+        if base is None or not hasattr(env, "action_repeat"):
+            raise ValueError("EpisodeStats needs a wrapped env (wrappers.wrap: EpisodeWrapper + AutoResetWrapper)")
+        if self._bufs is None or self._bufs[:2] != (base.num_envs, base.device):
+            self.close()
+            n, dev = base.num_envs, base.device
+            self._bufs = (n, dev, _lib.DeviceBuffer(4 * 3 * n, dev), _lib.DeviceBuffer(4 * 4 * n, dev),
+                          _lib.DeviceBuffer(4 * 8, dev))
+        self._env = base
+        return base, self._bufs
+
+    def begin(self, env) -> None:
+        """Seeds the carry from the env's record (pp3_episode_stats_begin on the env's stream)."""
+        if self._pending:
+            self.read()
+        base, (n, dev, carry, _, _) = self._buffers(env)
+        ep, stride = base.device_field(_abi.F_EPISODE)
+        done, _ = base.device_field(_abi.F_DONE)
+        self._check(self._L.pp3_episode_stats_begin(dev, n, C.c_void_p(ep), stride, C.c_void_p(done), carry.ptr,
+                                                    C.c_void_p(base._L.pp3_stream(base._h))))
+
+    def add(self, env, comm=None) -> None:
+        """The last collect_ppo batch's rows (pp3_episode_stats_rows on the env's stream; with comm,
+        then the rank sum of out4).  Nothing waits; `fetch` / `read` pick the result up."""
+        if self._pending:
+            raise ValueError("EpisodeStats.add: the previous batch was not read (begin() or read() first)")
+        base, (n, dev, carry, part, out) = self._buffers(env)
+        b = env.ppo_device_batch()
+        (rew, (K, nb)), (done, _), (trunc, _) = b["reward"], b["done"], b["truncation"]
+        if nb != n:
+            raise ValueError(f"the batch has {nb} envs, the statistics {n}")
+        stream = base._L.pp3_stream(base._h)
+        self._check(self._L.pp3_episode_stats_rows(dev, K, n, n, C.c_void_p(rew), C.c_void_p(done), C.c_void_p(trunc),
+                                                   int(env.action_repeat), carry.ptr, part.ptr, out.ptr,
+                                                   C.c_void_p(stream)))
+        self._src = 0
+        if comm is not None:
+            comm.sum_ranks_device(out.ptr.value, out.ptr.value + 16, 4, stream)
+            self._src = 16
+        self._pending = True
+
+    def fetch(self) -> None:
+        """Downloads the pending batch's four numbers and adds them to the accumulators; the caller
+        has already waited for the env's stream (train_iteration: behind metrics()' wait)."""
+        if not self._pending:
+            return
+        out = np.empty(4, np.float32)
+        _lib.check(self._L.pp3_memcpy_d2h(_vp(out), C.c_void_p(self._bufs[4].ptr.value + self._src), out.nbytes))
+        self._pending = False
+        self.last = out
+        self.count += int(out[0])
+        self.sum_reward += float(out[1])
+        self.length += float(out[2])
+        self.truncated += float(out[3])
+
+    def read(self) -> Tuple[int, Dict[str, float]]:
+        """(episodes finished, {"sum_reward", "length", "truncated"}: their sums) since the last reset()."""
+        if self._pending:
+            self._env.synchronize()
+            self.fetch()
+        return self.count, {"sum_reward": self.sum_reward, "length": self.length, "truncated": self.truncated}
+
+    def local_out4(self) -> np.ndarray:
+        """This rank's own four numbers of the last add() (before the rank sum); waits for the stream."""
+        self._env.synchronize()
+        out = np.empty(4, np.float32)
+        self._bufs[4].download(out)
+        return out
+
+    def carry(self) -> np.ndarray:
+        """The carry [3][N] (ret, len, pd) downloaded; waits for the stream."""
+        self._env.synchronize()
+        out = np.empty((3, self._bufs[0]), np.float32)
+        self._bufs[2].download(out)
+        return out
+
+    def metrics(self) -> Dict[str, float]:
+        """The episode/* keys of a report: the means over the finished episodes, the truncated
+        fraction and the count; with no episode, the count only."""
+        count, sums = self.read()
+        m: Dict[str, float] = {"episode/count": count}
+        if count:
+            m.update({"episode/sum_reward": sums["sum_reward"] / count, "episode/length": sums["length"] / count,
+                      "episode/truncated": sums["truncated"] / count})
+        return m
+
+    def close(self) -> None:
+        if self._bufs is not None:
+            for b in self._bufs[2:]:
+                b.free()
+            self._bufs = None
 
     def __del__(self):
         try:
@@ -718,7 +879,8 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
           deterministic_eval: bool = False, key, progress_fn: Optional[Callable[[int, Dict[str, Any]], None]] = None,
           policy_params_fn: Optional[Callable[..., None]] = None, shuffle: bool = True,
           max_grad_norm: Optional[float] = None, normalize_observations: bool = False, device_rng: bool = True,
-          comm=None, checkpoint_path=None, restore=None, **hparams):
+          comm=None, checkpoint_path=None, restore=None, log_training_metrics: bool = False,
+          reduce_eval_metrics: bool = False, **hparams):
     """Brax's ppo.train loop around `learner.train_iteration` (the schedule: eval_schedule).  `env`
     and `eval_env` are `wrappers.wrap`ped envs of this `episode_length` / `action_repeat`; `eval_env`
     may also be a constructed `evaluator.Evaluator` (e.g. one on the reward path), or None to train
@@ -733,7 +895,16 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
     `learner.deterministic_policy()`, rebuilt from the parameters at every evaluation; otherwise it
     samples from the actor.  normalize_observations: train_iteration(update_normalizer=True), which
     needs PPOLearner(running_statistics=True).  comm: every rank trains on its own shard with its own
-    key and evaluates its own eval env; the evaluation metrics are not reduced across ranks.
+    key and evaluates its own eval env; the evaluation metrics are this rank's unless
+    reduce_eval_metrics, which hands comm to the Evaluator that train builds: its mean / std keys then
+    cover all ranks' eval envs, every env weighing the same (evaluator's docstring).
+
+    log_training_metrics: at every epoch end the metrics gain episode/sum_reward and episode/length
+    (means over the episodes that ended in the epoch's rollouts), episode/truncated (their fraction
+    the episode length ended) and episode/count; with no finished episode, episode/count only.  The
+    accumulators (an EpisodeStats, summed over ranks under comm) then reset.  Brax reports the mean of
+    a deque of the last 100 episodes instead.  With eval_env=None, progress_fn(num_steps, metrics) is
+    then called at every epoch end with the training metrics (Brax's run_evals=False).
 
     checkpoint_path (a path, or a callable of num_steps returning one): after every evaluation --
     without an evaluator at the same epoch boundaries -- and after progress_fn and policy_params_fn,
@@ -785,7 +956,8 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
         evaluator = eval_env
     else:
         evaluator = Evaluator(eval_env, actor, episode_length, action_repeat, key=k_eval,
-                              deterministic=deterministic_eval)
+                              deterministic=deterministic_eval, comm=comm if reduce_eval_metrics else None)
+    stats = EpisodeStats() if log_training_metrics else None
     metrics: Dict[str, Any] = {}
     walltime = 0.0
     it, epoch0 = 0, 0
@@ -826,17 +998,25 @@ def train(learner: PPOLearner, env, eval_env=None, *, num_timesteps: int, episod
             state, losses, _ = learner.train_iteration(
                 env, state, k_it, actor, critic, unroll_length, num_minibatches=num_minibatches,
                 num_updates_per_batch=num_updates_per_batch, lr=float(lr), shuffle=shuffle, max_grad_norm=max_grad_norm,
-                update_normalizer=normalize_observations, comm=comm, device_rng=device_rng, **hparams)
+                update_normalizer=normalize_observations, comm=comm, device_rng=device_rng, episode_stats=stats,
+                **hparams)
             it += 1
         dt = time.time() - t0  # (train_iteration's metrics download has waited for the epoch's work)
         walltime += dt
         metrics = {f"training/{k}": v for k, v in losses.items()}
         metrics["training/sps"] = sched["iterations_per_epoch"] * sched["steps_per_iteration"] / dt
         metrics["training/walltime"] = walltime
+        if stats is not None:
+            metrics.update(stats.metrics())
+            stats.reset()
         if evaluator is not None:
             metrics = evaluate(it * sched["steps_per_iteration"], metrics)
+        elif stats is not None and progress_fn is not None:
+            progress_fn(it * sched["steps_per_iteration"], metrics)
         if checkpoint_path is not None:
             checkpoint(it * sched["steps_per_iteration"], epoch + 1)
     if evaluator is not None and evaluator is not eval_env:
         evaluator.close()
+    if stats is not None:
+        stats.close()
     return actor, critic, metrics

@@ -248,6 +248,24 @@ class Comm:
                                                             C.c_void_p(recv) if recv else None, int(count),
                                                             C.c_void_p(stream) if stream else None))
 
+    def sum_ranks_device(self, send: int, out: int, count: int, stream: Optional[int] = None) -> None:
+        """out[i] = the sum over ranks of `send`[i] (`count` f32 at device addresses), the same bits
+        on every rank: allgather_device into a [world][count] buffer this communicator keeps per
+        count, then pp3_sum_gathered_f32 (rank 0's value first, then + rank 1's, ...), both on
+        `stream` with no host synchronisation.  Every rank must call it.  For small vectors (the
+        evaluation's 22 sums, the training episode statistics' 4)."""
+        count = int(count)
+        bufs = self.__dict__.setdefault("_gathered", {})
+        if count not in bufs:
+            bufs[count] = self._lib.DeviceBuffer(4 * self.world * count, self.device)
+        recv = bufs[count].ptr.value
+        self.allgather_device(send, recv, count, stream)
+        rc = self._L.pp3_sum_gathered_f32(self.device, C.c_void_p(recv), self.world, count, C.c_void_p(out),
+                                          C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise self._lib.PupperHipError(
+                f"pupper_hip error {rc}: {self._L.pp3_ppo_last_error().decode(errors='replace')}")
+
     def allreduce(self, values, op: str = "max") -> np.ndarray:
         from . import _abi
         v = np.ascontiguousarray(values, dtype=np.float64).ravel()
@@ -264,6 +282,8 @@ class Comm:
         if getattr(self, "_h", None):
             self._L.pp3_comm_destroy(self._h)
             self._h = None
+        for b in self.__dict__.pop("_gathered", {}).values():
+            b.free()
 
     def __del__(self):
         try:

@@ -134,11 +134,12 @@ class AutoResetEpisodeEnv:
         return self.env.rollout_policy_sample(state, policy, nsteps, key, truncation=truncation)
 
     def collect_ppo(self, state: State, policy, value, nsteps: int, key, discount: float = 0.97,
-                    gae_lambda: float = 0.95, reward_scaling: float = 1.0):
+                    gae_lambda: float = 0.95, reward_scaling: float = 1.0, host_batch: bool = True):
         """One PPO batch of K wrapper steps with values and GAE targets (PupperV3Env.collect_ppo:
-        (state, batch, next_key))."""
+        (state, batch, next_key); host_batch=False: batch is None and nothing is waited for)."""
         self._prepare(state)
-        return self.env.collect_ppo(state, policy, value, nsteps, key, discount, gae_lambda, reward_scaling)
+        return self.env.collect_ppo(state, policy, value, nsteps, key, discount, gae_lambda, reward_scaling,
+                                    host_batch=host_batch)
 
     def ppo_device_batch(self):
         """PupperV3Env.ppo_device_batch: the last collect_ppo batch's device addresses."""
