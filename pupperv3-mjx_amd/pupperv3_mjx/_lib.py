@@ -19,6 +19,142 @@ class PupperHipError(RuntimeError):
     pass
 
 
+# The binding table: one line per entry point, "<restype>[?] <name> <argtypes ...>" in the codes of
+# CTYPES.  "?" marks an entry an older build of the library lacks (one loaded through PP3_LIB_PATH for
+# a kernel A/B): it is skipped when missing.  tests/test_abi.py holds every line against the prototype
+# in the header.
+_HEADER_TABLE = """
+n pp3_abi_version
+z pp3_struct_size n
+s pp3_last_error
+n pp3_device_count
+n pp3_create M E i i P
+n pp3_destroy p
+i pp3_num_envs p
+i pp3_state_stride p
+i pp3_env_device p
+n pp3_reset p p p p
+n pp3_step p p p
+n pp3_rollout p p l i p p p p
+n pp3_set_dr p p
+n pp3_set_pipeline_output p i
+n pp3_set_terrain p p i
+i pp3_terrain_slots p
+n pp3_physics_step p p i p
+n pp3_set_auto_reset p i
+n pp3_set_action_repeat p i
+n pp3_field p i P L
+n pp3_copy_field_to_host p i p z
+n pp3_copy_field_from_host p i p z
+n pp3_synchronize p
+n pp3_copy_field_to_host_async p i p z
+n pp3_outputs_to_host p p
+n pp3_host_device_ptr p P
+p pp3_stream p
+n? pp3_event_create p P
+n? pp3_event_record p p
+n? pp3_event_synchronize p
+n? pp3_event_destroy p
+n pp3_device_malloc i z P
+n pp3_device_free p
+n pp3_memcpy_h2d p p z
+n pp3_memcpy_d2h p p z
+n pp3_memcpy_d2d p p z p
+n pp3_memcpy_h2d_async p p z p
+n pp3_host_malloc z P
+n pp3_host_free p
+n pp3_fill_uniform p p l u u f f p
+n pp3_step_timed p p l i F
+n pp3_rollout_timed p p l i p p p F
+n pp3_render i p p i p i p p i i i F p p
+s pp3_render_last_error
+n pp3_policy_create i i i p p p P
+n pp3_policy_act p p l i p l p
+n pp3_policy_out_dim p
+n pp3_policy_destroy p
+n pp3_rollout_policy p p i p p p p p
+n pp3_rollout_policy_timed p p i p p p p F
+s pp3_policy_last_error
+n? pp3_policy_set_distribution p i f f
+n? pp3_policy_sample p p l i p i p l p p p p
+n? pp3_rollout_policy_sample p p i p p p p p p p p p
+n? pp3_rollout_policy_sample_timed p p i p p p p p p p p F
+n? pp3_set_truncation_trajectory p p i
+n? pp3_gae i i i l p p p p p f f f p p p
+s? pp3_ppo_last_error
+n? pp3_eval_reset i i p p
+n? pp3_eval_accumulate i i p p p l p l p p
+n? pp3_eval_accumulate_rows i i i l p p i i p p
+n? pp3_eval_reduce i i p p p
+n? pp3_sum_gathered_f32 i p i l p p
+n? pp3_eval_column_sums i i p p p p
+n? pp3_eval_finish i p i p p
+n? pp3_episode_stats_begin i i p l p p p
+n? pp3_episode_stats_rows i i i l p p p i p p p p
+n? pp3_learner_create i i i p p p i p p p f f l P
+n? pp3_learner_destroy p
+n? pp3_learner_buffers p i i P L
+n? pp3_ppo_loss_grad p i i i i p p p p p p p p p f f f f f i p p
+n? pp3_adam_step p f f f f f f p
+n? pp3_policy_load_params p p i i p p p p
+s? pp3_learn_last_error
+n? pp3_learner_normalizer_update p p l f f f p p p p
+n? pp3_learner_set_env_index p p i p
+n? pp3_ppo_loss_grad_indexed p i i i i p p p p p p p p p f f f f f i p p
+n? pp3_grad_clip p f p p
+n? pp3_learner_allreduce_grads p p p p
+n? pp3_learner_reduce_gathered p p i p p
+n? pp3_learner_normalizer_update_ranks p p p l f f f p p p p
+n? pp3_learner_draw_noise p p i i i P p
+n? pp3_permute_by_bits i p i p p
+n? pp3_learner_shuffle_env_index p p i i p
+n? pp3_learner_rng_buffers p P I P L
+n? pp3_learner_init_params p p i p
+n pp3_comm_unique_id p
+n pp3_comm_init p i i i P
+n pp3_comm_destroy p
+i pp3_comm_rank p
+i pp3_comm_world p
+s pp3_comm_last_error
+n pp3_gather p p i i p p
+n pp3_gather_rollout p p p p p i i i p p
+n? pp3_comm_allgather_f32 p p p l p
+i? pp3_comm_device p
+n pp3_comm_allreduce p p p i i
+n pp3_comm_barrier p
+"""
+# include/pupper_hip_diag.h: diagnostic entry points (per-phase / per-wave clocks of a -DPP3_PHASE_PROF
+# build; the product library exports them only to return PP3_ERR_ARG)
+_DIAG_TABLE = """
+n pp3_phase_profile Q i i
+n pp3_wave_profile U i
+i? pp3_rollout_policy_fused p
+i? pp3_narrow_cull p
+i? pp3_diag_step_variant p i i
+"""
+# code -> (kind the header must declare, ctypes type); the upper-case codes are typed pointers
+CTYPES = {
+    "n": ("int", C.c_int), "i": ("int32", C.c_int32), "l": ("int64", C.c_int64), "u": ("uint32", C.c_uint32),
+    "z": ("size_t", C.c_size_t), "f": ("float", C.c_float), "p": ("pointer", C.c_void_p), "s": ("pointer", C.c_char_p),
+    "P": ("pointer", C.POINTER(C.c_void_p)), "F": ("pointer", C.POINTER(C.c_float)),
+    "I": ("pointer", C.POINTER(C.c_int32)), "L": ("pointer", C.POINTER(C.c_int64)),
+    "U": ("pointer", C.POINTER(C.c_uint32)), "Q": ("pointer", C.POINTER(C.c_uint64)),
+    "M": ("pointer", C.POINTER(_abi.Model)), "E": ("pointer", C.POINTER(_abi.EnvConfig)),
+}
+
+
+def _parse(table: str) -> dict:
+    """{name: (restype code, argtype codes, optional)} of a table above."""
+    rows = (line.split() for line in table.strip().splitlines())
+    return {r[1]: (r[0][0], tuple(r[2:]), r[0].endswith("?")) for r in rows}
+
+
+BINDINGS = _parse(_HEADER_TABLE)
+EXPORTED_SYMBOLS = tuple(BINDINGS)
+DIAG_SYMBOLS = tuple(_parse(_DIAG_TABLE))
+BINDINGS.update(_parse(_DIAG_TABLE))
+
+
 def load() -> C.CDLL:
     global _lib
     if _lib is not None:
@@ -28,176 +164,12 @@ def load() -> C.CDLL:
             f"HIP extension not built: {LIB_PATH} is missing (run __graft_entry__.build() or make -C "
             "pupperv3-mjx_amd/csrc); there is no CPU fallback for the environment step.")
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
-    L.pp3_abi_version.restype = C.c_int
-    L.pp3_struct_size.argtypes = [C.c_int]
-    L.pp3_struct_size.restype = sz
-    L.pp3_last_error.restype = C.c_char_p
-    L.pp3_device_count.restype = C.c_int
-    L.pp3_create.argtypes = [C.POINTER(_abi.Model), C.POINTER(_abi.EnvConfig), i32, i32, C.POINTER(vp)]
-    L.pp3_destroy.argtypes = [vp]
-    L.pp3_num_envs.argtypes = [vp]
-    L.pp3_num_envs.restype = i32
-    L.pp3_state_stride.argtypes = [vp]
-    L.pp3_state_stride.restype = i32
-    L.pp3_env_device.argtypes = [vp]
-    L.pp3_env_device.restype = i32
-    L.pp3_reset.argtypes = [vp, vp, vp, vp]
-    L.pp3_step.argtypes = [vp, vp, vp]
-    L.pp3_rollout.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
-    L.pp3_set_dr.argtypes = [vp, vp]
-    L.pp3_set_pipeline_output.argtypes = [vp, i32]
-    L.pp3_physics_step.argtypes = [vp, vp, i32, vp]
-    L.pp3_field.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
-    L.pp3_copy_field_to_host.argtypes = [vp, i32, vp, sz]
-    L.pp3_copy_field_from_host.argtypes = [vp, i32, vp, sz]
-    L.pp3_synchronize.argtypes = [vp]
-    L.pp3_copy_field_to_host_async.argtypes = [vp, i32, vp, sz]
-    L.pp3_host_malloc.argtypes = [sz, C.POINTER(vp)]
-    L.pp3_memcpy_h2d_async.argtypes = [vp, vp, sz, vp]
-    L.pp3_host_free.argtypes = [vp]
-    L.pp3_device_malloc.argtypes = [i32, sz, C.POINTER(vp)]
-    L.pp3_device_free.argtypes = [vp]
-    L.pp3_memcpy_h2d.argtypes = [vp, vp, sz]
-    L.pp3_memcpy_d2h.argtypes = [vp, vp, sz]
-    L.pp3_outputs_to_host.argtypes = [vp, vp]
-    L.pp3_host_device_ptr.argtypes = [vp, C.POINTER(vp)]
-    L.pp3_memcpy_d2d.argtypes = [vp, vp, sz, vp]
-    L.pp3_fill_uniform.argtypes = [vp, vp, i64, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp]
-    L.pp3_step_timed.argtypes = [vp, vp, i64, i32, C.POINTER(C.c_float)]
-    L.pp3_rollout_timed.argtypes = [vp, vp, i64, i32, vp, vp, vp, C.POINTER(C.c_float)]
-    L.pp3_phase_profile.argtypes = [C.POINTER(C.c_uint64), i32, i32]
-    L.pp3_wave_profile.argtypes = [C.POINTER(C.c_uint32), i32]
-    if hasattr(L, "pp3_rollout_policy_fused"):  # (diagnostic query; absent from pre-round-5 builds used in A/B)
-        L.pp3_rollout_policy_fused.argtypes = [vp]
-        L.pp3_rollout_policy_fused.restype = i32
-    if hasattr(L, "pp3_narrow_cull"):  # (diagnostic query; absent from pre-round-6 builds used in A/B)
-        L.pp3_narrow_cull.argtypes = [vp]
-        L.pp3_narrow_cull.restype = i32
-    if hasattr(L, "pp3_diag_step_variant"):  # (diagnostic query; absent from pre-round-9 builds used in A/B)
-        L.pp3_diag_step_variant.argtypes = [vp, i32, i32]
-        L.pp3_diag_step_variant.restype = i32
-    L.pp3_set_auto_reset.argtypes = [vp, i32]
-    L.pp3_set_action_repeat.argtypes = [vp, i32]
-    L.pp3_policy_create.argtypes = [i32, i32, i32, vp, vp, vp, C.POINTER(vp)]
-    L.pp3_policy_act.argtypes = [vp, vp, i64, i32, vp, i64, vp]
-    L.pp3_policy_out_dim.argtypes = [vp]
-    L.pp3_policy_destroy.argtypes = [vp]
-    L.pp3_rollout_policy.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
-    L.pp3_rollout_policy_timed.argtypes = [vp, vp, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
-    L.pp3_policy_last_error.restype = C.c_char_p
-    if hasattr(L, "pp3_policy_sample"):  # (the stochastic head; absent from earlier builds run in kernel A/B)
-        L.pp3_policy_set_distribution.argtypes = [vp, i32, C.c_float, C.c_float]
-        L.pp3_policy_sample.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, vp, vp, vp, vp]
-        L.pp3_rollout_policy_sample.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.pp3_rollout_policy_sample_timed.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
-        for name in ("pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample",
-                     "pp3_rollout_policy_sample_timed"):
-            getattr(L, name).restype = C.c_int
-    if hasattr(L, "pp3_gae"):  # (the PPO batch; absent from earlier builds run in kernel A/B)
-        f32 = C.c_float
-        L.pp3_set_truncation_trajectory.argtypes = [vp, vp, i32]
-        L.pp3_gae.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp]
-        L.pp3_set_truncation_trajectory.restype = C.c_int
-        L.pp3_gae.restype = C.c_int
-        L.pp3_ppo_last_error.restype = C.c_char_p
-    if hasattr(L, "pp3_ppo_loss_grad"):  # (the PPO learner; absent from earlier builds run in kernel A/B)
-        f32 = C.c_float
-        L.pp3_learner_create.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, f32, f32, i64, C.POINTER(vp)]
-        L.pp3_learner_destroy.argtypes = [vp]
-        L.pp3_learner_buffers.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(i64)]
-        L.pp3_ppo_loss_grad.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32,
-                                        f32, i32, vp, vp]
-        L.pp3_adam_step.argtypes = [vp, f32, f32, f32, f32, f32, f32, vp]
-        L.pp3_policy_load_params.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
-        for name in ("pp3_learner_create", "pp3_learner_destroy", "pp3_learner_buffers", "pp3_ppo_loss_grad",
-                     "pp3_adam_step", "pp3_policy_load_params"):
-            getattr(L, name).restype = C.c_int
-        L.pp3_learn_last_error.restype = C.c_char_p
-    if hasattr(L, "pp3_grad_clip"):  # (normaliser, env index, clip; absent from earlier builds run in kernel A/B)
-        f32 = C.c_float
-        L.pp3_learner_normalizer_update.argtypes = [vp, vp, i64, f32, f32, f32, vp, vp, vp, vp]
-        L.pp3_learner_set_env_index.argtypes = [vp, vp, i32, vp]
-        L.pp3_ppo_loss_grad_indexed.argtypes = L.pp3_ppo_loss_grad.argtypes
-        L.pp3_grad_clip.argtypes = [vp, f32, vp, vp]
-        for name in ("pp3_learner_normalizer_update", "pp3_learner_set_env_index", "pp3_ppo_loss_grad_indexed",
-                     "pp3_grad_clip"):
-            getattr(L, name).restype = C.c_int
-    if hasattr(L, "pp3_learner_allreduce_grads"):  # (the learner across ranks; absent from earlier builds run in A/B)
-        f32 = C.c_float
-        L.pp3_learner_allreduce_grads.argtypes = [vp, vp, vp, vp]
-        L.pp3_learner_reduce_gathered.argtypes = [vp, vp, i32, vp, vp]
-        L.pp3_learner_normalizer_update_ranks.argtypes = [vp, vp, vp, i64, f32, f32, f32, vp, vp, vp, vp]
-        L.pp3_comm_allgather_f32.argtypes = [vp, vp, vp, i64, vp]
-        L.pp3_comm_device.argtypes = [vp]
-        L.pp3_comm_device.restype = i32
-        for name in ("pp3_learner_allreduce_grads", "pp3_learner_reduce_gathered",
-                     "pp3_learner_normalizer_update_ranks", "pp3_comm_allgather_f32"):
-            getattr(L, name).restype = C.c_int
-    if hasattr(L, "pp3_learner_draw_noise"):  # (the device draws; absent from earlier builds run in kernel A/B)
-        L.pp3_learner_draw_noise.argtypes = [vp, vp, i32, i32, i32, C.POINTER(vp), vp]
-        L.pp3_permute_by_bits.argtypes = [i32, vp, i32, vp, vp]
-        L.pp3_learner_shuffle_env_index.argtypes = [vp, vp, i32, i32, vp]
-        L.pp3_learner_rng_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i64)]
-        for name in ("pp3_learner_draw_noise", "pp3_permute_by_bits", "pp3_learner_shuffle_env_index",
-                     "pp3_learner_rng_buffers"):
-            getattr(L, name).restype = C.c_int
-    if hasattr(L, "pp3_learner_init_params"):  # (network initialisation; absent from earlier builds run in kernel A/B)
-        L.pp3_learner_init_params.argtypes = [vp, vp, i32, vp]
-        L.pp3_learner_init_params.restype = C.c_int
-    if hasattr(L, "pp3_eval_reduce"):  # (the PPO evaluator; absent from earlier builds run in kernel A/B)
-        L.pp3_eval_reset.argtypes = [i32, i32, vp, vp]
-        L.pp3_eval_accumulate.argtypes = [i32, i32, vp, vp, vp, i64, vp, i64, vp, vp]
-        L.pp3_eval_accumulate_rows.argtypes = [i32, i32, i32, i64, vp, vp, i32, i32, vp, vp]
-        L.pp3_eval_reduce.argtypes = [i32, i32, vp, vp, vp]
-        for name in ("pp3_eval_reset", "pp3_eval_accumulate", "pp3_eval_accumulate_rows", "pp3_eval_reduce"):
-            getattr(L, name).restype = C.c_int
-    if hasattr(L, "pp3_episode_stats_rows"):  # (the PPO metrics; absent from earlier builds run in kernel A/B)
-        L.pp3_sum_gathered_f32.argtypes = [i32, vp, i32, i64, vp, vp]
-        L.pp3_eval_column_sums.argtypes = [i32, i32, vp, vp, vp, vp]
-        L.pp3_eval_finish.argtypes = [i32, vp, i32, vp, vp]
-        L.pp3_episode_stats_begin.argtypes = [i32, i32, vp, i64, vp, vp, vp]
-        L.pp3_episode_stats_rows.argtypes = [i32, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]
-        for name in ("pp3_sum_gathered_f32", "pp3_eval_column_sums", "pp3_eval_finish", "pp3_episode_stats_begin",
-                     "pp3_episode_stats_rows"):
-            getattr(L, name).restype = C.c_int
-    L.pp3_stream.argtypes = [vp]
-    L.pp3_stream.restype = vp
-    if hasattr(L, "pp3_event_create"):  # (absent from pre-round-5 builds run in kernel A/B: no host-API step there)
-        L.pp3_event_create.argtypes = [vp, C.POINTER(vp)]
-        L.pp3_event_record.argtypes = [vp, vp]
-        L.pp3_event_synchronize.argtypes = [vp]
-        L.pp3_event_destroy.argtypes = [vp]
-        for name in ("pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy"):
-            getattr(L, name).restype = C.c_int
-    L.pp3_set_terrain.argtypes = [vp, vp, i32]
-    L.pp3_terrain_slots.argtypes = [vp]
-    L.pp3_terrain_slots.restype = i32
-    # multi-GPU (pp3_comm.hip; RCCL is dlopen'ed by the library on first use)
-    L.pp3_comm_unique_id.argtypes = [vp]
-    L.pp3_comm_init.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
-    L.pp3_comm_destroy.argtypes = [vp]
-    L.pp3_comm_rank.argtypes = [vp]
-    L.pp3_comm_rank.restype = i32
-    L.pp3_comm_world.argtypes = [vp]
-    L.pp3_comm_world.restype = i32
-    L.pp3_comm_last_error.restype = C.c_char_p
-    L.pp3_gather.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.pp3_gather_rollout.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    L.pp3_render.argtypes = [i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(C.c_float), vp, vp]
-    L.pp3_render_last_error.restype = C.c_char_p
-    L.pp3_comm_allreduce.argtypes = [vp, vp, vp, i32, i32]
-    L.pp3_comm_barrier.argtypes = [vp]
-    for name in ("pp3_create", "pp3_destroy", "pp3_reset", "pp3_step", "pp3_rollout", "pp3_rollout_timed", "pp3_set_dr", "pp3_set_pipeline_output",
-                 "pp3_physics_step", "pp3_field", "pp3_copy_field_to_host", "pp3_copy_field_from_host",
-                 "pp3_synchronize", "pp3_copy_field_to_host_async", "pp3_host_malloc", "pp3_host_free",
-                 "pp3_memcpy_h2d_async",
-                 "pp3_device_malloc", "pp3_device_free", "pp3_memcpy_h2d", "pp3_memcpy_d2h",
-                 "pp3_outputs_to_host", "pp3_host_device_ptr", "pp3_memcpy_d2d", "pp3_fill_uniform", "pp3_step_timed", "pp3_phase_profile",
-                 "pp3_wave_profile", "pp3_set_auto_reset", "pp3_set_action_repeat", "pp3_policy_create", "pp3_policy_act", "pp3_policy_destroy", "pp3_rollout_policy",
-                 "pp3_rollout_policy_timed", "pp3_set_terrain", "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_gather", "pp3_gather_rollout",
-                 "pp3_comm_allreduce", "pp3_comm_barrier", "pp3_render"):
-        getattr(L, name).restype = C.c_int
+    for name, (ret, args, optional) in BINDINGS.items():
+        if optional and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.restype = CTYPES[ret][1]
+        fn.argtypes = [CTYPES[a][1] for a in args]
     if L.pp3_abi_version() != _abi.ABI_VERSION:
         raise PupperHipError("ABI version mismatch between libpupper_hip.so and pupperv3_mjx/_abi.py")
     if L.pp3_struct_size(0) != C.sizeof(_abi.Model) or L.pp3_struct_size(1) != C.sizeof(_abi.EnvConfig):
@@ -206,50 +178,16 @@ def load() -> C.CDLL:
     return L
 
 
-def check(rc: int) -> None:
+_LAST_ERROR = {"env": "pp3_last_error", "policy": "pp3_policy_last_error", "ppo": "pp3_ppo_last_error",
+               "learn": "pp3_learn_last_error", "comm": "pp3_comm_last_error", "render": "pp3_render_last_error"}
+
+
+def check(rc: int, domain: str = "env") -> None:
+    """Raises PupperHipError with the library's message for a non-zero return code; `domain` names the
+    part of the library whose pp3_*_last_error holds it."""
     if rc != 0:
-        msg = load().pp3_last_error().decode(errors="replace")
+        msg = getattr(load(), _LAST_ERROR[domain])().decode(errors="replace")
         raise PupperHipError(f"pupper_hip error {rc}: {msg}")
-
-
-def check_comm(rc: int) -> None:
-    if rc != 0:
-        msg = load().pp3_comm_last_error().decode(errors="replace")
-        raise PupperHipError(f"pupper_hip comm error {rc}: {msg}")
-
-
-EXPORTED_SYMBOLS = (
-    "pp3_abi_version", "pp3_struct_size", "pp3_last_error", "pp3_device_count", "pp3_create", "pp3_destroy",
-    "pp3_num_envs", "pp3_state_stride", "pp3_env_device", "pp3_reset", "pp3_step", "pp3_rollout", "pp3_set_dr",
-    "pp3_set_pipeline_output", "pp3_physics_step", "pp3_field", "pp3_copy_field_to_host", "pp3_copy_field_from_host", "pp3_synchronize",
-    "pp3_copy_field_to_host_async", "pp3_host_malloc", "pp3_host_free", "pp3_memcpy_h2d_async",
-    "pp3_device_malloc", "pp3_device_free", "pp3_memcpy_h2d", "pp3_memcpy_d2h", "pp3_outputs_to_host", "pp3_host_device_ptr", "pp3_memcpy_d2d",
-    "pp3_fill_uniform", "pp3_step_timed", "pp3_rollout_timed", "pp3_set_auto_reset", "pp3_set_action_repeat",
-    "pp3_policy_create", "pp3_policy_act", "pp3_policy_out_dim", "pp3_policy_destroy", "pp3_policy_last_error",
-    "pp3_rollout_policy", "pp3_rollout_policy_timed",
-    "pp3_policy_set_distribution", "pp3_policy_sample", "pp3_rollout_policy_sample", "pp3_rollout_policy_sample_timed",
-    "pp3_set_truncation_trajectory", "pp3_gae", "pp3_ppo_last_error",
-    "pp3_eval_reset", "pp3_eval_accumulate", "pp3_eval_accumulate_rows", "pp3_eval_reduce",
-    "pp3_sum_gathered_f32", "pp3_eval_column_sums", "pp3_eval_finish", "pp3_episode_stats_begin",
-    "pp3_episode_stats_rows",
-    "pp3_learner_create", "pp3_learner_destroy", "pp3_learner_buffers", "pp3_ppo_loss_grad", "pp3_adam_step",
-    "pp3_policy_load_params", "pp3_learn_last_error",
-    "pp3_learner_normalizer_update", "pp3_learner_set_env_index", "pp3_ppo_loss_grad_indexed", "pp3_grad_clip",
-    "pp3_learner_allreduce_grads", "pp3_learner_reduce_gathered", "pp3_learner_normalizer_update_ranks",
-    "pp3_comm_allgather_f32", "pp3_comm_device",
-    "pp3_learner_draw_noise", "pp3_permute_by_bits", "pp3_learner_shuffle_env_index", "pp3_learner_rng_buffers",
-    "pp3_learner_init_params",
-    "pp3_stream", "pp3_event_create", "pp3_event_record", "pp3_event_synchronize", "pp3_event_destroy",
-    "pp3_set_terrain", "pp3_terrain_slots",
-    "pp3_comm_unique_id", "pp3_comm_init", "pp3_comm_destroy", "pp3_comm_rank", "pp3_comm_world",
-    "pp3_comm_last_error", "pp3_gather", "pp3_gather_rollout", "pp3_comm_allreduce", "pp3_comm_barrier",
-    "pp3_render", "pp3_render_last_error",
-)
-
-# include/pupper_hip_diag.h: diagnostic entry points (per-phase / per-wave clocks of a -DPP3_PHASE_PROF
-# build; the product library exports them only to return PP3_ERR_ARG)
-DIAG_SYMBOLS = ("pp3_phase_profile", "pp3_wave_profile", "pp3_rollout_policy_fused", "pp3_narrow_cull",
-                "pp3_diag_step_variant")
 
 
 class BlockPool(list):
@@ -376,3 +314,24 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceBuffers:
+    """Named device buffers of one owner, kept between calls and grown on demand."""
+
+    def __init__(self, device: int = 0):
+        self.device = int(device)
+        self._bufs = {}
+
+    def get(self, name: str, nbytes: int) -> DeviceBuffer:
+        """The buffer kept under `name`; one too small is freed and allocated anew (its address changes)."""
+        b = self._bufs.get(name)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._bufs[name] = DeviceBuffer(nbytes, self.device)
+        return b
+
+    def free_all(self) -> None:
+        while self._bufs:
+            self._bufs.popitem()[1].free()

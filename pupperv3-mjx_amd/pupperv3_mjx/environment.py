@@ -20,6 +20,7 @@ numbers), all forced by the device-resident design:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import weakref
@@ -430,6 +431,8 @@ class PupperV3Env:
             body_mass=np.array(m.body_mass[:], dtype=np.float64),
         )
         self._h = None
+        self._dev = _lib.DeviceBuffers(self.device)  # the rollouts' device buffers, kept and grown (by name)
+        self._ppo_dev = None  # the last collect_ppo batch's device addresses (ppo_device_batch)
         self.stride = _abi.state_stride(c.latency_len, c.imu_latency_len)
         self._pipeline_output = bool(pipeline_output)
         if not create_device:  # host-only construction (tests/oracle tooling): structs, no GPU
@@ -564,16 +567,8 @@ class PupperV3Env:
         if getattr(self, "_h", None):
             self._L.pp3_destroy(self._h)
             self._h = None
-        for b in (getattr(self, "_roll_bufs", None) or (0, []))[1]:
-            b.free()
-        self._roll_bufs = None
-        for b in getattr(self, "_samp_bufs", None) or ():
-            b.free()
-        self._samp_bufs = None
-        for b in [getattr(self, "_trunc_buf", None)] + list(getattr(self, "_ppo_bufs", None) or ()):
-            if b is not None:
-                b.free()
-        self._trunc_buf = self._ppo_bufs = self._ppo_dev = None
+        self._dev.free_all()
+        self._ppo_dev = None
         # free page-locked blocks go with their pools; leased ones are freed when their arrays die
         if getattr(self, "_pin_pool", None) is not None:
             self._pin_pool.retire()
@@ -732,8 +727,7 @@ class PupperV3Env:
             self._write_state(state)
         # actions through a page-locked staging block of the ring; the launch that last read this
         # block has completed once its event has (at most ASYNC_DEPTH steps in flight)
-        slot = self._act_ring[self._act_i]
-        self._act_i = (self._act_i + 1) % len(self._act_ring)
+        slot = self._next_slot()
         slot.wait()
         np.copyto(slot.arr[:act.size], act.reshape(-1))
         if ACTIONS_ZERO_COPY:
@@ -784,8 +778,7 @@ class PupperV3Env:
             if not self.holds(state):
                 self._write_state(state)
             # a page-locked action block of the ring (reused once the launch that read it completed)
-            slot = self._act_ring[self._act_i]
-            self._act_i = (self._act_i + 1) % len(self._act_ring)
+            slot = self._next_slot()
             slot.wait()
             n, D, B = self.num_envs, self.observation_size, self._step_batch_len()
             lease = _lib.PinnedBlock.take(4 * B * n * (D + 2), self._batch_pool)
@@ -804,6 +797,12 @@ class PupperV3Env:
         qb.states.append(weakref.ref(st))
         qb.n += 1
         return st
+
+    def _next_slot(self) -> "_ActSlot":
+        """The next block of the page-locked action ring (round robin)."""
+        slot = self._act_ring[self._act_i]
+        self._act_i = (self._act_i + 1) % len(self._act_ring)
+        return slot
 
     def _step_batch_len(self) -> int:
         """Steps per queued batch: STEP_BATCH, fewer where its output block would exceed
@@ -866,43 +865,57 @@ class PupperV3Env:
         info["truncation"] after each step (all zeros without auto-reset), which `done` alone does
         not determine (pp3_set_truncation_trajectory)."""
         self._flush()
-        single = _single_of(state)
-        n, D = self.num_envs, self.observation_size
+        n = self.num_envs
         act = np.ascontiguousarray(np.asarray(actions, dtype=np.float32))
         if act.ndim < 2 or act.size % (n * _abi.NU):
             raise ValueError(f"actions must be [K, {n}, {_abi.NU}] (got {np.shape(actions)})")
         K = act.size // (n * _abi.NU)
+        buf = self._dev.get("action", act.nbytes)
+        return self._unroll(state, K, truncation, lambda reward, done, obs: self.rollout_device(
+            buf.ptr.value, n * _abi.NU, K, reward, done, obs), upload=(buf, act))
+
+    def _unroll(self, state: State, K: int, truncation: bool, launch, extras=(),
+                upload=None) -> Tuple[State, Dict[str, np.ndarray]]:
+        """What rollout, rollout_policy and rollout_policy_sample share: `state` onto the device if it
+        is not there, `launch(reward_ptr, done_ptr, obs_ptr)` (the K-step library call, given the
+        device addresses its trajectory goes to) with the truncation rows registered around it when
+        `truncation`, one wait, then (state after the last step, traj).  traj holds `extras`
+        ((name, device buffer, shape) arrays, downloaded), "obs", "reward", "done" and with
+        `truncation` "truncation", of a single-env state without the env axis.  `upload` = (device
+        buffer, host array) is copied up before the launch, and says that the launch takes the
+        device snapshot of the previous state itself (rollout_device)."""
+        single = _single_of(state)
+        n, D = self.num_envs, self.observation_size
         if not self.holds(state):
             self._write_state(state)
         blk = self._traj_block(K)
-        bufs = self._rollout_buffers(K, outputs=blk is None)
-        bufs[0].upload(act)
-        tb = self._trunc_begin(K) if truncation else None
         if blk is not None:
             # the trajectory lands in one page-locked block that the fused launch stores into through
             # its device mapping (no copy after the launch; the arrays are views that keep it leased)
             lease, (p_obs, p_rew, p_done) = blk
-            try:
-                self.rollout_device(bufs[0].ptr.value, n * _abi.NU, K, p_rew, p_done, p_obs)
-            finally:
-                self._trunc_end(tb)
-            self.synchronize()
-            obs, rew, done = self._traj_views(lease, K)
         else:  # a long unroll: device buffers, copied out after the launch
-            try:
-                self.rollout_device(bufs[0].ptr.value, n * _abi.NU, K, bufs[1].ptr.value, bufs[2].ptr.value,
-                                    bufs[3].ptr.value)
-            finally:
-                self._trunc_end(tb)
-            self.synchronize()
-            rew = np.empty((K, n), np.float32)
-            done = np.empty((K, n), np.float32)
-            obs = np.empty((K, n, D), np.float32)
-            for b, a in zip(bufs[1:], (rew, done, obs)):
-                b.download(a)
-        traj = {"obs": obs, "reward": rew, "done": done}
+            outs = [self._dev.get(name, 4 * K * n * w) for name, w in (("reward", 1), ("done", 1), ("obs", D))]
+            p_rew, p_done, p_obs = (b.ptr.value for b in outs)
+        if upload is not None:
+            upload[0].upload(upload[1])
+        else:
+            self._before_launch()
+        with self._truncation_rows(K, truncation) as tb:
+            launch(p_rew, p_done, p_obs)
+        self.synchronize()
+        traj = {name: np.empty(shape, np.float32) for name, _, shape in extras}
+        for name, b, _ in extras:
+            b.download(traj[name])
+        if blk is not None:
+            traj["obs"], traj["reward"], traj["done"] = self._traj_views(lease, K)
+        else:
+            traj.update(obs=np.empty((K, n, D), np.float32), reward=np.empty((K, n), np.float32),
+                        done=np.empty((K, n), np.float32))
+            for b, k in zip(outs, ("reward", "done", "obs")):
+                b.download(traj[k])
         if tb is not None:
-            traj["truncation"] = self._trunc_rows(tb, K)
+            traj["truncation"] = np.empty((K, n), np.float32)
+            tb.download(traj["truncation"])
         if single:
             traj = {k: v[:, 0] for k, v in traj.items()}
         return self._issue(single), traj
@@ -916,37 +929,10 @@ class PupperV3Env:
         "done": [K, N]} (single-env states: without the N axis), and with `truncation=True`
         "truncation" [K, N] as in rollout()."""
         self._flush()
-        single = _single_of(state)
-        n, D, K = self.num_envs, self.observation_size, int(nsteps)
-        if K < 1:
-            raise ValueError("nsteps must be >= 1")
-        if not self.holds(state):
-            self._write_state(state)
-        blk = self._traj_block(K)  # obs / reward / done straight into page-locked memory (see rollout)
-        bufs = self._rollout_buffers(K, outputs=blk is None)
-        self._before_launch()
-        outs = blk[1] if blk is not None else (bufs[3].ptr.value, bufs[1].ptr.value, bufs[2].ptr.value)
-        tb = self._trunc_begin(K) if truncation else None
-        try:
-            _lib.check(self._L.pp3_rollout_policy(self._h, policy._h, K, bufs[0].ptr, C.c_void_p(outs[1]),
-                                                  C.c_void_p(outs[2]), C.c_void_p(outs[0]), None))
-        finally:
-            self._trunc_end(tb)
-        self.synchronize()
-        traj = {"action": np.empty((K, n, _abi.NU), np.float32)}  # (the actions stay on the device for the steps)
-        bufs[0].download(traj["action"])
-        if blk is not None:
-            traj["obs"], traj["reward"], traj["done"] = self._traj_views(blk[0], K)
-        else:
-            traj.update(obs=np.empty((K, n, D), np.float32), reward=np.empty((K, n), np.float32),
-                        done=np.empty((K, n), np.float32))
-            for b, k in zip(bufs[1:], ("reward", "done", "obs")):
-                b.download(traj[k])
-        if tb is not None:
-            traj["truncation"] = self._trunc_rows(tb, K)
-        if single:
-            traj = {k: v[:, 0] for k, v in traj.items()}
-        return self._issue(single), traj
+        K = _nsteps(nsteps)
+        bufs = self._sample_buffers(K, ("action",))  # (the actions stay on the device for the steps)
+        return self._unroll(state, K, truncation, lambda reward, done, obs: _lib.check(self._L.pp3_rollout_policy(
+            self._h, policy._h, K, bufs[0][1].ptr, reward, done, obs, None)), bufs)
 
     def rollout_policy_sample(self, state: State, policy, nsteps: int, key,
                               truncation: bool = False) -> Tuple[State, Dict[str, np.ndarray], np.ndarray]:
@@ -971,44 +957,18 @@ class PupperV3Env:
         (extras.state_extras["truncation"], as in rollout()); collect_ppo returns the whole batch
         with values and GAE targets."""
         self._flush()
-        single = _single_of(state)
-        n, D, K = self.num_envs, self.observation_size, int(nsteps)
-        if K < 1:
-            raise ValueError("nsteps must be >= 1")
-        k_in = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
-        k_out = np.zeros(2, dtype=np.uint32)
-        if not self.holds(state):
-            self._write_state(state)
-        blk = self._traj_block(K)  # obs / reward / done straight into page-locked memory (see rollout)
-        bufs = self._rollout_buffers(K, outputs=blk is None)
-        sbuf = self._sample_buffers(K)
-        self._before_launch()
-        outs = blk[1] if blk is not None else (bufs[3].ptr.value, bufs[1].ptr.value, bufs[2].ptr.value)
-        tb = self._trunc_begin(K) if truncation else None
-        try:
-            _lib.check(self._L.pp3_rollout_policy_sample(
-                self._h, policy._h, K, k_in.ctypes.data_as(C.c_void_p), k_out.ctypes.data_as(C.c_void_p), bufs[0].ptr,
-                sbuf[0].ptr, sbuf[1].ptr, C.c_void_p(outs[1]), C.c_void_p(outs[2]), C.c_void_p(outs[0]), None))
-        finally:
-            self._trunc_end(tb)
-        self.synchronize()
-        traj = {"action": np.empty((K, n, _abi.NU), np.float32), "raw_action": np.empty((K, n, _abi.NU), np.float32),
-                "log_prob": np.empty((K, n), np.float32)}
-        bufs[0].download(traj["action"])
-        sbuf[0].download(traj["raw_action"])
-        sbuf[1].download(traj["log_prob"])
-        if blk is not None:
-            traj["obs"], traj["reward"], traj["done"] = self._traj_views(blk[0], K)
-        else:
-            traj.update(obs=np.empty((K, n, D), np.float32), reward=np.empty((K, n), np.float32),
-                        done=np.empty((K, n), np.float32))
-            for b, k in zip(bufs[1:], ("reward", "done", "obs")):
-                b.download(traj[k])
-        if tb is not None:
-            traj["truncation"] = self._trunc_rows(tb, K)
-        if single:
-            traj = {k: v[:, 0] for k, v in traj.items()}
-        return self._issue(single), traj, k_out
+        K, keys = _nsteps(nsteps), _key_pair(key)
+        bufs = self._sample_buffers(K)
+        return self._unroll(state, K, truncation, lambda reward, done, obs: self._launch_sample(
+            policy, K, keys, bufs, reward, done, obs), bufs) + (keys[1],)
+
+    def _launch_sample(self, policy, K: int, keys, bufs, reward: int, done: int, obs: int) -> None:
+        """pp3_rollout_policy_sample on the env's stream: keys = (K_0, K_nsteps out), bufs =
+        _sample_buffers(K), the trajectory to the device addresses reward / done / obs."""
+        vp = C.c_void_p
+        _lib.check(self._L.pp3_rollout_policy_sample(
+            self._h, policy._h, K, keys[0].ctypes.data_as(vp), keys[1].ctypes.data_as(vp), bufs[0][1].ptr,
+            bufs[1][1].ptr, bufs[2][1].ptr, reward, done, obs, None))
 
     def collect_ppo(self, state: State, policy, value, nsteps: int, key, discount: float = 0.97,
                     gae_lambda: float = 0.95, reward_scaling: float = 1.0,
@@ -1033,53 +993,44 @@ class PupperV3Env:
         behind the batch's launches and wait for them when first read, as a step()'s do."""
         self._flush()
         single = _single_of(state)
-        n, D, K = self.num_envs, self.observation_size, int(nsteps)
-        if K < 1:
-            raise ValueError("nsteps must be >= 1")
+        n, D, K = self.num_envs, self.observation_size, _nsteps(nsteps)
         if value.out_dim != 1 or value.in_dim != D:
             raise ValueError(f"the value network must map {D} inputs to 1 output "
                              f"(got {value.in_dim} -> {value.out_dim}; export.convert_value_params)")
         if not all(np.isfinite(x) for x in (discount, gae_lambda, reward_scaling)):
             raise ValueError("discount, gae_lambda and reward_scaling must be finite")
-        k_in = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
-        k_out = np.zeros(2, dtype=np.uint32)
+        keys = _key_pair(key)
         if not self.holds(state):
             self._write_state(state)
-        act_buf = self._rollout_buffers(K, outputs=False)[0]
-        sbuf = self._sample_buffers(K)
-        obs_all, val_all, rew, done, vs, adv = (b.ptr.value for b in self._ppo_buffers(K))
+        bufs = self._sample_buffers(K)
+        # obs_all [K+1][N][36H], values_all [K+1][N]; reward, done, value targets and advantages [K][N]
+        obs_all, val_all, rew, done, vs, adv = (
+            self._dev.get("ppo_" + name, 4 * rows * n * w).ptr.value for name, rows, w in (
+                ("obs", K + 1, D), ("value", K + 1, 1), ("reward", K, 1), ("done", K, 1), ("target", K, 1),
+                ("advantage", K, 1)))
         self._before_launch()
         stream = self._L.pp3_stream(self._h)
         obs_ptr, _ = self.device_field(_abi.F_OBS)
         _lib.check(self._L.pp3_memcpy_d2d(C.c_void_p(obs_all), C.c_void_p(obs_ptr), 4 * n * D, C.c_void_p(stream)))
-        tb = self._trunc_begin(K)
-        try:
-            _lib.check(self._L.pp3_rollout_policy_sample(
-                self._h, policy._h, K, k_in.ctypes.data_as(C.c_void_p), k_out.ctypes.data_as(C.c_void_p), act_buf.ptr,
-                sbuf[0].ptr, sbuf[1].ptr, C.c_void_p(rew), C.c_void_p(done), C.c_void_p(obs_all + 4 * n * D), None))
-        finally:
-            self._trunc_end(tb)
+        with self._truncation_rows(K) as tb:
+            self._launch_sample(policy, K, keys, bufs, rew, done, obs_all + 4 * n * D)
         value.act(obs_all, D, (K + 1) * n, val_all, 1, stream)  # row K: the bootstrap value
-        rc = self._L.pp3_gae(self.device, K, n, n, C.c_void_p(rew), C.c_void_p(done), tb.ptr, C.c_void_p(val_all),
-                             C.c_void_p(val_all + 4 * K * n), float(discount), float(gae_lambda), float(reward_scaling),
-                             C.c_void_p(vs), C.c_void_p(adv), C.c_void_p(stream))
-        if rc != 0:
-            raise _lib.PupperHipError(f"pupper_hip error {rc}: {self._L.pp3_ppo_last_error().decode(errors='replace')}")
-        self._ppo_dev = {
-            "observation": (obs_all, (K, n, D)), "obs": (obs_all + 4 * n * D, (K, n, D)),
-            "action": (act_buf.ptr.value, (K, n, _abi.NU)), "raw_action": (sbuf[0].ptr.value, (K, n, _abi.NU)),
-            "log_prob": (sbuf[1].ptr.value, (K, n)), "reward": (rew, (K, n)), "done": (done, (K, n)),
-            "truncation": (tb.ptr.value, (K, n)), "value": (val_all, (K, n)),
-            "bootstrap_value": (val_all + 4 * K * n, (n,)), "value_target": (vs, (K, n)), "advantage": (adv, (K, n))}
+        _lib.check(self._L.pp3_gae(self.device, K, n, n, C.c_void_p(rew), C.c_void_p(done), tb.ptr, C.c_void_p(val_all),
+                                   C.c_void_p(val_all + 4 * K * n), float(discount), float(gae_lambda),
+                                   float(reward_scaling), C.c_void_p(vs), C.c_void_p(adv), C.c_void_p(stream)), "ppo")
+        self._ppo_dev = {name: (b.ptr.value, shape) for name, b, shape in bufs}
+        self._ppo_dev.update({
+            "observation": (obs_all, (K, n, D)), "obs": (obs_all + 4 * n * D, (K, n, D)), "reward": (rew, (K, n)),
+            "done": (done, (K, n)), "truncation": (tb.ptr.value, (K, n)), "value": (val_all, (K, n)),
+            "bootstrap_value": (val_all + 4 * K * n, (n,)), "value_target": (vs, (K, n)), "advantage": (adv, (K, n))})
         if not host_batch:
             # obs | reward | done of the state by one kernel into a page-locked block, then the
             # completion event of a ring slot: the returned state waits for it on first read
             lease = _lib.PinnedBlock.take(4 * n * (D + 2), self._pin_pool)
             _lib.check(self._L.pp3_outputs_to_host(self._h, C.c_void_p(lease.ptr.value)))
-            slot = self._act_ring[self._act_i]
-            self._act_i = (self._act_i + 1) % len(self._act_ring)
+            slot = self._next_slot()
             slot.record()
-            return self._issue(single, lease, slot), None, k_out
+            return self._issue(single, lease, slot), None, keys[1]
         self.synchronize()
         host = {"obs_all": np.empty((K + 1, n, D), np.float32), "val_all": np.empty((K + 1, n), np.float32)}
         for name, ptr in (("obs_all", obs_all), ("val_all", val_all)):
@@ -1092,61 +1043,37 @@ class PupperV3Env:
         if single:
             batch = {k: v[:, 0] for k, v in batch.items()}
         batch["bootstrap_value"] = host["val_all"][K, 0] if single else host["val_all"][K]
-        return self._issue(single), batch, k_out
+        return self._issue(single), batch, keys[1]
 
     def ppo_device_batch(self) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
         """{name: (device address, shape)} of the last collect_ppo batch (f32, C order, the batched
         shapes), for a learner on the same GPU; valid until the next collect_ppo or rollout* call."""
-        if getattr(self, "_ppo_dev", None) is None:
+        if self._ppo_dev is None:
             raise ValueError("ppo_device_batch: no collect_ppo batch on the device yet")
         return dict(self._ppo_dev)
 
-    def _ppo_buffers(self, K: int) -> list:
-        """Device buffers of collect_ppo(): obs_all [K+1][N][36H], values_all [K+1][N], reward, done,
-        value targets and advantages [K][N]; kept and grown."""
-        cur = getattr(self, "_ppo_bufs", None)
-        n, D = self.num_envs, self.observation_size
-        sizes = [4 * (K + 1) * n * D, 4 * (K + 1) * n] + [4 * K * n] * 4
-        if cur is None or any(b.nbytes < s for b, s in zip(cur, sizes)):
-            if cur is not None:
-                for b in cur:
-                    b.free()
-            cur = [_lib.DeviceBuffer(sz, self.device) for sz in sizes]
-            self._ppo_bufs = cur
-        return cur
+    @contextlib.contextmanager
+    def _truncation_rows(self, K: int, on: bool = True):
+        """Registers the truncation row buffer for one K-step rollout launch and yields it (None
+        without `on`); unregisters it afterwards, also when the launch raises: step() and every other
+        rollout write no truncation rows."""
+        if not on:
+            yield None
+            return
+        tb = self._dev.get("truncation", 4 * K * self.num_envs)
+        _lib.check(self._L.pp3_set_truncation_trajectory(self._h, tb.ptr, K))
+        try:
+            yield tb
+        finally:
+            if self._h:  # (a closed env has nothing registered)
+                _lib.check(self._L.pp3_set_truncation_trajectory(self._h, None, 0))
 
-    def _trunc_begin(self, K: int):
-        """Registers the truncation row buffer (kept and grown) for one K-step rollout launch."""
-        cur = getattr(self, "_trunc_buf", None)
-        if cur is None or cur.nbytes < 4 * K * self.num_envs:
-            if cur is not None:
-                cur.free()
-            cur = self._trunc_buf = _lib.DeviceBuffer(4 * K * self.num_envs, self.device)
-        _lib.check(self._L.pp3_set_truncation_trajectory(self._h, cur.ptr, K))
-        return cur
-
-    def _trunc_end(self, tb) -> None:
-        """Unregisters it: step() and every other rollout write no truncation rows."""
-        if tb is not None and self._h:
-            _lib.check(self._L.pp3_set_truncation_trajectory(self._h, None, 0))
-
-    def _trunc_rows(self, tb, K: int) -> np.ndarray:
-        out = np.empty((K, self.num_envs), np.float32)
-        tb.download(out)
-        return out
-
-    def _sample_buffers(self, K: int) -> list:
-        """Device buffers of rollout_policy_sample(): raw actions and log-probs for K steps; kept and grown."""
-        cur = getattr(self, "_samp_bufs", None)
+    def _sample_buffers(self, K: int, names=("action", "raw_action", "log_prob")) -> list:
+        """(name, device buffer, shape) of the per-step arrays a policy rollout leaves on the device:
+        actions, and of a sampling one the raw actions and log-probs."""
         n = self.num_envs
-        sizes = [4 * K * n * _abi.NU, 4 * K * n]
-        if cur is None or any(b.nbytes < s for b, s in zip(cur, sizes)):
-            if cur is not None:
-                for b in cur:
-                    b.free()
-            cur = [_lib.DeviceBuffer(sz, self.device) for sz in sizes]
-            self._samp_bufs = cur
-        return cur
+        shapes = {"action": (K, n, _abi.NU), "raw_action": (K, n, _abi.NU), "log_prob": (K, n)}
+        return [(k, self._dev.get(k, 4 * math.prod(shapes[k])), shapes[k]) for k in names]
 
     def _traj_block(self, K: int):
         """A page-locked block for a K-step trajectory [obs K x N x 36H | reward K x N | done K x N] and
@@ -1169,20 +1096,6 @@ class PupperV3Env:
         flat = np.asarray(lease)
         return (flat[:K * n * D].reshape(K, n, D), flat[K * n * D:K * n * (D + 1)].reshape(K, n),
                 flat[K * n * (D + 1):].reshape(K, n))  # (read-only: a lease's arrays are)
-
-    def _rollout_buffers(self, K: int, outputs: bool) -> list:
-        """Device buffers of rollout(): actions for K steps, and with `outputs` the reward, done and
-        obs trajectories (only for unrolls too long for the page-locked block); kept and grown."""
-        cur = getattr(self, "_roll_bufs", None)
-        n, D = self.num_envs, self.observation_size
-        sizes = [4 * K * n * _abi.NU] + ([4 * K * n, 4 * K * n, 4 * K * n * D] if outputs else [])
-        if cur is None or len(cur[1]) < len(sizes) or any(b.nbytes < s for b, s in zip(cur[1], sizes)):
-            if cur is not None:
-                for b in cur[1]:
-                    b.free()
-            cur = (K, [_lib.DeviceBuffer(sz, self.device) for sz in sizes])
-            self._roll_bufs = cur
-        return cur[1]
 
     def holds(self, state: State) -> bool:
         """The device buffers hold exactly `state`: the last state this env issued, unedited, and
@@ -1351,6 +1264,18 @@ class PupperV3Env:
         put(io, info["imu_buffer"], 6 * Li)
         self._put(_abi.F_STATE, rec)
         self._put(_abi.F_OBS, np.asarray(state.obs, dtype=np.float32).reshape(n, -1))
+
+
+def _nsteps(nsteps) -> int:
+    K = int(nsteps)
+    if K < 1:
+        raise ValueError("nsteps must be >= 1")
+    return K
+
+
+def _key_pair(key) -> Tuple[np.ndarray, np.ndarray]:
+    """(K_0, the array the library stores K_nsteps into) of a sampling rollout."""
+    return np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2)), np.zeros(2, dtype=np.uint32)
 
 
 def _single_of(state) -> bool:

@@ -86,8 +86,7 @@ class Evaluator:
 
     # ---- launches ---------------------------------------------------------------------------
     def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise _lib.PupperHipError(f"pupper_hip error {rc}: {self._L.pp3_ppo_last_error().decode(errors='replace')}")
+        _lib.check(rc, "ppo")
 
     def _unroll_chunk(self, policy, nsteps: int, key, reward, done):
         """nsteps wrapper steps with the policy in the loop, no observation trajectory; -> the next key."""

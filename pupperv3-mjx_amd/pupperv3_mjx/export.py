@@ -262,10 +262,8 @@ class DevicePolicy:
         self._L = L
         in_dim, o, a, w = layers_blob(policy)
         h = C.c_void_p()
-        rc = L.pp3_policy_create(int(device), in_dim, len(o), o.ctypes.data_as(C.c_void_p),
-                                 a.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), C.byref(h))
-        if rc != 0:
-            raise _lib.PupperHipError(L.pp3_policy_last_error().decode())
+        _lib.check(L.pp3_policy_create(int(device), in_dim, len(o), o.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p),
+                                       w.ctypes.data_as(C.c_void_p), C.byref(h)), "policy")
         self._h = h
         self.in_dim = in_dim
         self.out_dim = int(o[-1])
@@ -276,17 +274,18 @@ class DevicePolicy:
             if dist.get("type") != "normal_tanh":
                 self.close()
                 raise ValueError(f"unsupported distribution {dist.get('type')!r} (device: 'normal_tanh')")
-            rc = L.pp3_policy_set_distribution(h, DIST_NORMAL_TANH, float(dist["min_std"]), float(dist["var_scale"]))
-            if rc != 0:
+            try:
+                _lib.check(L.pp3_policy_set_distribution(h, DIST_NORMAL_TANH, float(dist["min_std"]),
+                                                         float(dist["var_scale"])), "policy")
+            except _lib.PupperHipError:
                 self.close()
-                raise _lib.PupperHipError(L.pp3_policy_last_error().decode())
+                raise
             self.distribution = dict(dist)
 
     def act(self, obs_dev: int, obs_stride: int, n: int, actions_dev: int, action_stride: int, stream=None) -> None:
-        rc = self._L.pp3_policy_act(self._h, C.c_void_p(obs_dev), int(obs_stride), int(n), C.c_void_p(actions_dev),
-                                    int(action_stride), C.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise self._lib.PupperHipError(self._L.pp3_policy_last_error().decode())
+        self._lib.check(self._L.pp3_policy_act(
+            self._h, C.c_void_p(obs_dev), int(obs_stride), int(n), C.c_void_p(actions_dev), int(action_stride),
+            C.c_void_p(stream) if stream else None), "policy")
 
     def act_env(self, env, actions_dev: int, stream=None) -> None:
         """actions[N][12] = policy(env's current observation buffer)."""
@@ -304,11 +303,10 @@ class DevicePolicy:
         action_stride) = tanh(raw); raw [n][12], log_prob [n] and logits [n][24] where given."""
         k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
         p = lambda v: C.c_void_p(v) if v else None
-        rc = self._L.pp3_policy_sample(self._h, C.c_void_p(obs_dev), int(obs_stride), int(n), k.ctypes.data_as(C.c_void_p),
-                                       int(bool(partitionable)), C.c_void_p(actions_dev), int(action_stride), p(raw_dev),
-                                       p(logp_dev), p(logits_dev), C.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise self._lib.PupperHipError(self._L.pp3_policy_last_error().decode())
+        self._lib.check(self._L.pp3_policy_sample(
+            self._h, C.c_void_p(obs_dev), int(obs_stride), int(n), k.ctypes.data_as(C.c_void_p), int(bool(partitionable)),
+            C.c_void_p(actions_dev), int(action_stride), p(raw_dev), p(logp_dev), p(logits_dev),
+            C.c_void_p(stream) if stream else None), "policy")
 
     def sample_env(self, env, key, actions_dev: int, raw_dev: int = 0, logp_dev: int = 0, logits_dev: int = 0,
                    stream=None) -> None:

@@ -125,11 +125,9 @@ class PPOLearner:
         self._shapes = ((pin, pout, pact), (vin, vout, vact))
         self.distribution = dict(dist)
         h = C.c_void_p()
-        rc = L.pp3_learner_create(self.device, pin, len(pout), _vp(pout), _vp(pact), _vp(pblob), len(vout), _vp(vout),
-                                  _vp(vact), _vp(vblob), float(dist["min_std"]), float(dist["var_scale"]),
-                                  self.max_rows, C.byref(h))
-        if rc != 0:
-            raise _lib.PupperHipError(L.pp3_learn_last_error().decode())
+        _lib.check(L.pp3_learner_create(
+            self.device, pin, len(pout), _vp(pout), _vp(pact), _vp(pblob), len(vout), _vp(vout), _vp(vact), _vp(vblob),
+            float(dist["min_std"]), float(dist["var_scale"]), self.max_rows, C.byref(h)), "learn")
         self._h = h
         self._norm = None  # rows: mean, std, summed_variance
         self.running_statistics = bool(running_statistics)
@@ -177,8 +175,7 @@ class PPOLearner:
         return C.c_void_p(stream) if stream else None
 
     def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise _lib.PupperHipError(f"pupper_hip error {rc}: {self._L.pp3_learn_last_error().decode(errors='replace')}")
+        _lib.check(rc, "learn")
 
     def _wait(self) -> None:
         if self._env is not None:
@@ -642,8 +639,7 @@ class EpisodeStats:
         self.count, self.sum_reward, self.length, self.truncated = 0, 0.0, 0.0, 0.0
 
     def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise _lib.PupperHipError(f"pupper_hip error {rc}: {self._L.pp3_ppo_last_error().decode(errors='replace')}")
+        _lib.check(rc, "ppo")
 
     def _buffers(self, env):
         base = getattr(env, "env", None)

@@ -323,10 +323,8 @@ def render_qpos(scene: Scene, qposes: Sequence[np.ndarray], camera="tracking_cam
             try:
                 xf_b.upload(xf)
                 cam_b.upload(cams)
-                rc = L.pp3_render(device, tri_b.ptr, own_b.ptr, len(scene.tris), rgb_b.ptr, ng, xf_b.ptr, cam_b.ptr, F,
-                                  height, width, sp.ctypes.data_as(C.POINTER(C.c_float)), out_b.ptr, None)
-                if rc != 0:
-                    raise _lib.PupperHipError(f"pp3_render error {rc}: {L.pp3_render_last_error().decode()}")
+                _lib.check(L.pp3_render(device, tri_b.ptr, own_b.ptr, len(scene.tris), rgb_b.ptr, ng, xf_b.ptr, cam_b.ptr,
+                                        F, height, width, sp.ctypes.data_as(C.POINTER(C.c_float)), out_b.ptr, None), "render")
                 img = np.empty((F, height, width, 3), np.uint8)
                 out_b.download(img)
                 frames += list(img)

@@ -197,7 +197,7 @@ class Comm:
 
         def make_id():
             buf = (C.c_uint8 * _abi.COMM_ID_BYTES)()
-            _lib.check_comm(L.pp3_comm_unique_id(buf))
+            _lib.check(L.pp3_comm_unique_id(buf), "comm")
             return bytes(buf)
 
         self._h = None
@@ -205,7 +205,7 @@ class Comm:
             uid = rendezvous_id(self.rank, self.world, make_id, tag)
             ubuf = (C.c_uint8 * len(uid)).from_buffer_copy(uid)
             h = C.c_void_p()
-            _lib.check_comm(L.pp3_comm_init(ubuf, self.rank, self.world, self.device, C.byref(h)))
+            _lib.check(L.pp3_comm_init(ubuf, self.rank, self.world, self.device, C.byref(h)), "comm")
             self._h = h
             self._tag = tag
             self.barrier()  # every rank has read the id: rank 0 may remove the file
@@ -225,9 +225,9 @@ class Comm:
         """Learner batch of every rank's shard into dst_dev (see module doc); root < 0 = all-gather."""
         if hasattr(env, "_flush"):
             env._flush()  # a step() launch still queued (environment.DEFER_LAUNCH) first
-        self._lib.check_comm(self._L.pp3_gather(self._h, env._h, int(nmax), int(root),
-                                                C.c_void_p(dst_dev) if dst_dev else None,
-                                                C.c_void_p(stream) if stream else None))
+        self._lib.check(self._L.pp3_gather(self._h, env._h, int(nmax), int(root),
+                                           C.c_void_p(dst_dev) if dst_dev else None,
+                                           C.c_void_p(stream) if stream else None), "comm")
 
     def gather_rollout(self, env, traj_obs: int, traj_reward: int, traj_done: int, nsteps: int, nmax: int,
                        dst_dev: Optional[int], root: int = 0, stream: Optional[int] = None) -> None:
@@ -236,17 +236,17 @@ class Comm:
         if hasattr(env, "_flush"):
             env._flush()
         vp = C.c_void_p
-        self._lib.check_comm(self._L.pp3_gather_rollout(self._h, env._h, vp(traj_obs), vp(traj_reward), vp(traj_done),
-                                                        int(nsteps), int(nmax), int(root),
-                                                        vp(dst_dev) if dst_dev else None,
-                                                        vp(stream) if stream else None))
+        self._lib.check(self._L.pp3_gather_rollout(self._h, env._h, vp(traj_obs), vp(traj_reward), vp(traj_done),
+                                                   int(nsteps), int(nmax), int(root),
+                                                   vp(dst_dev) if dst_dev else None,
+                                                   vp(stream) if stream else None), "comm")
 
     def allgather_device(self, send: int, recv: int, count: int, stream: Optional[int] = None) -> None:
         """pp3_comm_allgather_f32: this rank's `count` f32 at device address `send` to slot `rank` of
         `recv` ([world][count] on this device) on every rank, on `stream`, with no host synchronisation."""
-        self._lib.check_comm(self._L.pp3_comm_allgather_f32(self._h, C.c_void_p(send) if send else None,
-                                                            C.c_void_p(recv) if recv else None, int(count),
-                                                            C.c_void_p(stream) if stream else None))
+        self._lib.check(self._L.pp3_comm_allgather_f32(self._h, C.c_void_p(send) if send else None,
+                                                       C.c_void_p(recv) if recv else None, int(count),
+                                                       C.c_void_p(stream) if stream else None), "comm")
 
     def sum_ranks_device(self, send: int, out: int, count: int, stream: Optional[int] = None) -> None:
         """out[i] = the sum over ranks of `send`[i] (`count` f32 at device addresses), the same bits
@@ -260,23 +260,20 @@ class Comm:
             bufs[count] = self._lib.DeviceBuffer(4 * self.world * count, self.device)
         recv = bufs[count].ptr.value
         self.allgather_device(send, recv, count, stream)
-        rc = self._L.pp3_sum_gathered_f32(self.device, C.c_void_p(recv), self.world, count, C.c_void_p(out),
-                                          C.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise self._lib.PupperHipError(
-                f"pupper_hip error {rc}: {self._L.pp3_ppo_last_error().decode(errors='replace')}")
+        self._lib.check(self._L.pp3_sum_gathered_f32(self.device, C.c_void_p(recv), self.world, count, C.c_void_p(out),
+                                                     C.c_void_p(stream) if stream else None), "ppo")
 
     def allreduce(self, values, op: str = "max") -> np.ndarray:
         from . import _abi
         v = np.ascontiguousarray(values, dtype=np.float64).ravel()
         out = np.empty_like(v)
-        self._lib.check_comm(self._L.pp3_comm_allreduce(
+        self._lib.check(self._L.pp3_comm_allreduce(
             self._h, v.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), v.size,
-            _abi.REDUCE_MAX if op == "max" else _abi.REDUCE_SUM))
+            _abi.REDUCE_MAX if op == "max" else _abi.REDUCE_SUM), "comm")
         return out
 
     def barrier(self) -> None:
-        self._lib.check_comm(self._L.pp3_comm_barrier(self._h))
+        self._lib.check(self._L.pp3_comm_barrier(self._h), "comm")
 
     def close(self) -> None:
         if getattr(self, "_h", None):

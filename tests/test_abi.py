@@ -94,3 +94,51 @@ def test_loopback_transport_exports_the_rccl_api():
         assert hasattr(T, name), name
     src = open(os.path.join(here, "..", "pupperv3-mjx_amd", "csrc", "pp3_comm.hip")).read()
     assert "#ifdef PP3_TEST_RCCL_SONAME" in src  # the product build always loads librccl
+
+
+_SCALAR_KINDS = {"int": "int", "int32_t": "int32", "int64_t": "int64", "uint32_t": "uint32", "size_t": "size_t",
+                 "float": "float"}
+
+
+def _kind(decl: str) -> str:
+    """The kind of one C parameter or return type: a pointer (also a parameter written as an array,
+    `const uint32_t key[2]`), else its scalar type."""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = [w for w in re.findall(r"\w+", decl) if w != "const"]
+    return _SCALAR_KINDS[words[0]]  # (KeyError: a type the binding table has no code for)
+
+
+def _prototypes(path):
+    """{name: (return kind, [argument kinds])} of every pp3_* prototype in a header."""
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    out = {}
+    for ret, name, args in re.findall(r"^[ \t]*([A-Za-z_][\w \t\*]*?)\b(pp3_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        ret = " ".join(w for w in ret.split() if w not in ("extern", "PP3_API"))
+        args = [a.strip() for a in args.split(",")]
+        out[name] = (_kind(ret), [] if args == ["void"] else [_kind(a) for a in args])
+    return out
+
+
+def test_binding_table_matches_the_prototypes():
+    """Every entry of _lib.BINDINGS against its prototype: the return kind, the argument count and
+    each argument's kind (pointer, int32, int64, uint32, size_t, float, int).  The header text and
+    the table only: no library is loaded."""
+    protos = dict(_prototypes(HEADER))
+    diag = _prototypes(DIAG_HEADER)
+    assert set(protos) == set(_lib.EXPORTED_SYMBOLS) and set(diag) == set(_lib.DIAG_SYMBOLS)
+    protos.update(diag)
+    assert set(protos) == set(_lib.BINDINGS) and len(protos) > 100
+    for name, (ret, args, optional) in _lib.BINDINGS.items():
+        want_ret, want_args = protos[name]
+        assert _lib.CTYPES[ret][0] == want_ret, (name, "return", _lib.CTYPES[ret][0], want_ret)
+        got = [_lib.CTYPES[a][0] for a in args]
+        assert got == want_args, (name, got, want_args)
+    # the codes' ctypes types are of their kinds
+    sizes = {"int": C.sizeof(C.c_int), "int32": 4, "int64": 8, "uint32": 4, "size_t": C.sizeof(C.c_size_t), "float": 4,
+             "pointer": C.sizeof(C.c_void_p)}
+    for code, (kind, ctype) in _lib.CTYPES.items():
+        assert C.sizeof(ctype) == sizes[kind], code
+        assert (kind == "pointer") == (ctype in (C.c_void_p, C.c_char_p) or hasattr(ctype, "contents")), code
+    assert _lib.CTYPES["f"][1] is C.c_float and _lib.CTYPES["u"][1] is C.c_uint32 and _lib.CTYPES["l"][1] is C.c_int64
